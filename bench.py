@@ -15,6 +15,11 @@ drop the other sectors' rays.  No collective runs on the data path — the devic
 border-brick reduce over RCCL (tsdf_map.distributed.border_reduce) is a read-out operation, timed
 separately (readout_merge_ms).
 
+A plain run sets up, warms up, times `--steps` steps and prints the line; `--dump-outputs DIR`
+also writes the timed context's field after the last step (dump_outputs).  The legs that take runs
+of their own -- the serial leg behind `roofline` / `serial_kernel_ms_per_launch`, `parity` against
+the CPU oracle and `cpu_baseline` -- run only with `--full` and are null in a plain run's line.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -98,6 +103,15 @@ def parse():
                     help="do not record per-kernel HIP events in the timed region")
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic_r06.json"),
                     help="PMC-measured HBM bytes per launch (from a separate rocprofv3 --pmc run)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs that take runs of their own: the "
+                         "serial leg (every kernel alone, the roofline), the parity check against "
+                         "the CPU oracle and the CPU baseline (--no-profile / --no-cpu / "
+                         "--parity-steps 0 still switch single legs off); a plain run only sets "
+                         "up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the field the timed context holds after its "
+                         "last step as DIR/<name>.npy (dump_outputs)")
     return ap.parse_args()
 
 
@@ -179,6 +193,34 @@ def bench_parity(args, steps, make_volume):
         out["sdf_mismatch_voxels"] = int(np.count_nonzero(gs.view(np.uint32) != os_.view(np.uint32)))
         out["max_abs_dsdf"] = float(np.max(np.abs(gs - os_)))
     return out
+
+
+DUMP_BRICKS = 8192  # sampled bricks of a dump: 2 x 8192 x 512 f32 = 32 MiB
+
+
+def dump_outputs(vol, out_dir, suffix=""):
+    """--dump-outputs: what a caller of the timed path holds after the last timed step, the
+    brick map of the timed context (export_bricks: every allocated brick in (z, y, x) order), as
+    .npy files.  The whole map can be gigabytes, so the bricks are a fixed sample -- the
+    DUMP_BRICKS bricks whose coordinates hash lowest, a choice that depends on nothing but each
+    brick's own coordinates -- next to float64 totals over every brick:
+      brick_coords  (m, 3) float64   brick coordinates of the sample, (z, y, x) order
+      brick_sdf     (m, 8, 8, 8) float32   S of the sample [z, y, x]; 0 where W == 0
+      brick_weight  (m, 8, 8, 8) float32   W of the sample
+      field_totals  (4,) float64   bricks, voxels with W > 0, sum of W, sum of |S| over W > 0
+    """
+    coords, s, w = vol.export_bricks()
+    seen = w > 0
+    s = np.where(seen, s, np.float32(0))
+    totals = np.array([coords.shape[0], np.count_nonzero(seen), w.sum(dtype=np.float64),
+                       np.abs(s).sum(dtype=np.float64)], np.float64)
+    c = coords.astype(np.uint64)  # two's complement of the int32 coordinates
+    h = (c[:, 0] * 73856093 ^ c[:, 1] * 19349663 ^ c[:, 2] * 83492791) & 0xFFFFFFFF
+    sel = np.sort(np.argsort(h, kind="stable")[:DUMP_BRICKS])
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("brick_coords", coords[sel].astype(np.float64)), ("brick_sdf", s[sel]),
+                    ("brick_weight", w[sel]), ("field_totals", totals)):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def lib_sha16():
@@ -273,20 +315,18 @@ def main():
     steps = []
     t_gen = time.time()
     for s in range(n_steps):
-        parts, offs, origins = [], [0], []
-        for j in range(scans_per_step):
-            k = s * scans_per_step + j
-            pts, org = sim.scan(k)
-            parts.append(pts)
-            offs.append(offs[-1] + pts.shape[0])
-            if args.semantics == "voxblox":
-                # the full pose (x, y, z, qx, qy, qz, qw): Voxblox's 1/z^2 weight needs the sensor
-                # axes (the yaw of pose_on_circle; tsdf_integrate_batch_device_pose)
-                yaw = pose_on_circle(k, hz=args.hz)[1]
-                org = np.concatenate([org, [0.0, 0.0, math.sin(yaw / 2), math.cos(yaw / 2)]])
-            origins.append(org)
-        steps.append((torch.cat(parts).contiguous(), np.array(offs, np.uint64),
-                      np.stack(origins)))
+        # the step's scans in one pass (TorchOusterSim.scans: scan(k)'s values bit for bit, without
+        # the per-scan launch overhead, which would dominate the set-up of a long run)
+        k0 = s * scans_per_step
+        x, offs, origins = sim.scans(k0, scans_per_step)
+        if args.semantics == "voxblox":
+            # the full pose (x, y, z, qx, qy, qz, qw): Voxblox's 1/z^2 weight needs the sensor
+            # axes (the yaw of pose_on_circle; tsdf_integrate_batch_device_pose)
+            yaws = [pose_on_circle(k0 + j, hz=args.hz)[1] for j in range(scans_per_step)]
+            origins = np.stack([np.concatenate([org, [0.0, 0.0, math.sin(yaw / 2),
+                                                      math.cos(yaw / 2)]])
+                                for org, yaw in zip(origins, yaws)])
+        steps.append((x, offs, origins))
     torch.cuda.synchronize()
     t_gen = time.time() - t_gen
     max_pts = max(int(np.diff(o).max()) for _, o, _ in steps)
@@ -324,7 +364,8 @@ def main():
         vol.set_profiling_period([], PROFILE_PERIOD)
         timing = {"every_launch": [], "all_kernels_every_nth_batch": PROFILE_PERIOD,
                   "method": "dispatch timestamps (hipExtLaunchKernel start/stop events)",
-                  "roofline_kernel_times": "serial leg (pipeline 0, every launch timed)"}
+                  "roofline_kernel_times": ("serial leg (pipeline 0, every launch timed)"
+                                            if args.full else None)}
     vol.reset_stats()
 
     # ---- timed region ---------------------------------------------------------------------------
@@ -353,6 +394,9 @@ def main():
     total_scans = args.steps * scans_per_step
     value = total_scans / elapsed
 
+    if args.dump_outputs:
+        dump_outputs(vol, args.dump_outputs, "_rank%d" % rank if world > 1 else "")
+
     # ---- roofline of the dominant kernel (per-launch means, this rank) -------------------------
     # One launch = one batch of scans.  Algorithmic bytes: per scan
     # B_scan = 12 N_valid + 16 U_vox (every valid ray's xyz read once, every voxel the scan updates
@@ -372,7 +416,7 @@ def main():
     kernel_ms_per_launch = {k: (kms[k] / st["kernel_launches"][k]) for k in kms
                             if st["kernel_launches"][k] > 0}
     serial = None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         vol_serial_ms, serial_launches = serial_kernel_times(args, steps, make_volume)
         serial = {k: round(v, 5) for k, v in vol_serial_ms.items()}
         # the dominant kernel: the largest of the kernels' durations ALONE
@@ -421,14 +465,15 @@ def main():
     # the bench's exact settings (semantics, pipeline, batch size, device batch API), against the
     # CPU oracle on the same scans (rank 0, N=1; after the timed region, never inside it) ---------
     parity = None
-    if rank == 0 and world == 1 and n_shards == 1 and not args.no_cpu and args.parity_steps > 0:
+    if (args.full and rank == 0 and world == 1 and n_shards == 1 and not args.no_cpu
+            and args.parity_steps > 0):
         parity = bench_parity(args, steps, make_volume)
 
     # ---- CPU baseline: the oracle on a bounded sample of the same workload (rank 0, N=1) --------
     # Two legs: the partitioned multi-threaded oracle on the box's CPU share (the
     # reported value) and the serial oracle (VDBFusion's serial Integrate loop), same scans.
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         import oracle
 

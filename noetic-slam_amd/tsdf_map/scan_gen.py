@@ -163,15 +163,16 @@ class TorchOusterSim:
         self.order = torch.as_tensor(base.order, device=device)
 
     def _intersect(self, o, d):
+        """o, d: (..., 3); any leading dimensions (one scan or a stack of scans)."""
         torch = self.torch
-        inf = torch.full_like(o[:, 0], float("inf"))
-        tg = (GROUND_Z - o[:, 2]) / d[:, 2]
+        inf = torch.full_like(o[..., 0], float("inf"))
+        tg = (GROUND_Z - o[..., 2]) / d[..., 2]
         t = torch.where((tg > 0) & torch.isfinite(tg), tg, inf)
 
         def cyl(cx, cy, r, inside):
-            ox, oy = o[:, 0] - cx, o[:, 1] - cy
-            a = d[:, 0] ** 2 + d[:, 1] ** 2
-            b = 2 * (ox * d[:, 0] + oy * d[:, 1])
+            ox, oy = o[..., 0] - cx, o[..., 1] - cy
+            a = d[..., 0] ** 2 + d[..., 1] ** 2
+            b = 2 * (ox * d[..., 0] + oy * d[..., 1])
             c = ox * ox + oy * oy - r * r
             disc = b * b - 4 * a * c
             sq = torch.sqrt(torch.clamp(disc, min=0))
@@ -202,6 +203,44 @@ class TorchOusterSim:
         sel = self.order[keep]
         pts = xyz[sel] @ R.T + P
         return pts.to(torch.float32), pos.astype(np.float64)
+
+    def scans(self, k0, n, chunk=64):
+        """Scans k0 .. k0+n-1 as one cloud: (float32 (sum n_i, 3) world xyz on device, scan after
+        scan; uint64 offsets (n+1,) numpy; float64 origins (n, 3) numpy).  The same values as
+        scan(k), bit for bit: the elementwise work (the scene intersection, the range rounding,
+        the LUT) runs once on a stack of `chunk` scans instead of once per scan; the rotations
+        and the noise stay the per-scan calls of scan(), on the same shapes."""
+        torch = self.torch
+        parts, counts, origins = [], [], []
+        for c0 in range(k0, k0 + n, chunk):
+            ks = range(c0, min(c0 + chunk, k0 + n))
+            poses = [pose_on_circle(k, hz=self.hz) for k in ks]
+            R = torch.as_tensor(np.stack([_rot_z(yaw) for _, yaw in poses]), dtype=torch.float64,
+                                device=self.device)
+            P = torch.as_tensor(np.stack([pos for pos, _ in poses]), dtype=torch.float64,
+                                device=self.device)
+            o = torch.stack([self.off @ R[i].T + P[i] for i in range(len(ks))])
+            d = torch.stack([self.udir @ R[i].T for i in range(len(ks))])
+            t = self._intersect(o, d)
+            if self.noise_m > 0:
+                g = torch.Generator(device=self.device)
+                noise = torch.empty_like(t)
+                for i, k in enumerate(ks):
+                    g.manual_seed(int(k))
+                    torch.randn(t.shape[1:], generator=g, dtype=torch.float64, device=self.device,
+                                out=noise[i])
+                t = t + self.noise_m * noise
+            r = torch.where(torch.isfinite(t) & (t > 0), torch.round(t * 1000.0),
+                            torch.zeros_like(t)).clamp(max=2 ** 20 - 1)
+            xyz = r[..., None] * self.dir + self.off
+            keep = (r != 0)[:, self.order]
+            for i in range(len(ks)):
+                sel = self.order[keep[i]]
+                parts.append((xyz[i][sel] @ R[i].T + P[i]).to(torch.float32))
+                counts.append(sel.shape[0])
+            origins.extend(pos.astype(np.float64) for pos, _ in poses)
+        offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.uint64)
+        return torch.cat(parts).contiguous(), offs, np.stack(origins)
 
 
 def single_ray_scan(points, origin=(0.0, 0.0, 0.0)):

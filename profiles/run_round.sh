@@ -23,14 +23,14 @@ fi
 if [ "$WHAT" != tests ]; then
   bash profiles/collect_pmc.sh "$OUT/pmc" > "$OUT/pmc.log" 2>&1
   cp "$OUT/pmc/traffic.json" "$OUT/traffic.json"
-  timeout -k 10 300 python3 bench.py --traffic-json "$OUT/traffic.json" > "$OUT/bench.out" 2> "$OUT/bench.err"
+  timeout -k 10 300 python3 bench.py --full --traffic-json "$OUT/traffic.json" > "$OUT/bench.out" 2> "$OUT/bench.err"
   grep '^{' "$OUT/bench.out" > "$OUT/bench.json"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rocprof" -o bench -- \
-      python3 bench.py --no-cpu --traffic-json "$OUT/traffic.json" > "$OUT/rocprof_bench.out" 2>&1
+      python3 bench.py --full --no-cpu --traffic-json "$OUT/traffic.json" > "$OUT/rocprof_bench.out" 2>&1
   find "$OUT/rocprof" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats.csv" \;
   rm -rf "$OUT/rocprof"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/rocprof" -o bench -- \
-      python3 bench.py --no-cpu --pipeline 0 --traffic-json "$OUT/traffic.json" > "$OUT/rocprof_serial.out" 2>&1
+      python3 bench.py --full --no-cpu --pipeline 0 --traffic-json "$OUT/traffic.json" > "$OUT/rocprof_serial.out" 2>&1
   find "$OUT/rocprof" -name '*kernel_stats.csv' -exec cp {} "$OUT/kernel_stats_serial.csv" \;
   rm -rf "$OUT/rocprof"
   cat "$OUT/bench.json"
