@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/tsdf_hip.h"
+#include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
 #include "pack_pool.h"
 #include "tsdf_device.h"
@@ -305,6 +306,9 @@ struct tsdf_ctx {
     uint32_t* brd_sent = nullptr;
     uint64_t brd_n_sent = 0;
     std::vector<std::pair<uint32_t*, uint64_t>> brd_backup;
+    // tsdf_align_terms_device's workgroup partials and their sum (launch_align), allocated at the
+    // first call
+    double* align_part = nullptr;
 };
 
 // A context with an open border reduce refuses new mass until the reduce is committed or aborted
@@ -1112,6 +1116,7 @@ void tsdf_destroy(tsdf_ctx* c) {
     }
     if (c->metrics) fclose(c->metrics);
     if (c->brd_sent) (void)hipFree(c->brd_sent);
+    if (c->align_part) (void)hipFree(c->align_part);
     for (auto& b : c->brd_backup) (void)hipFree(b.first);
     delete c->timer;
     delete c->pack;
@@ -2187,6 +2192,115 @@ int tsdf_query_dense(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], floa
     (void)hipFree(ds);
     if (dw) (void)hipFree(dw);
     if (e != hipSuccess) return fail(c, TSDF_EHIP, "query_dense: %s", hipGetErrorString(e));
+    return TSDF_OK;
+}
+
+// ---- sparse map queries (include/tsdf_hip_sample.h) ---------------------------------------------
+
+// the argument rules the sampling entry points share
+static int sample_args(tsdf_ctx* c, int32_t mode, float min_weight) {
+    if (mode != TSDF_SAMPLE_NEAREST && mode != TSDF_SAMPLE_TRILINEAR)
+        return fail(c, TSDF_EINVAL, "sample: mode must be TSDF_SAMPLE_NEAREST or _TRILINEAR");
+    if (!(min_weight >= 0.0f)) return fail(c, TSDF_EINVAL, "sample: min_weight is negative or NaN");
+    if (c->p.n_sectors > 1)
+        return fail(c, TSDF_EINVAL, "sample: the context holds one sector shard of the map "
+                                    "(n_sectors > 1); sampling a sharded field is not supported");
+    if (border_busy(c)) return TSDF_EINVAL;
+    return TSDF_OK;
+}
+
+int tsdf_sample_device(tsdf_ctx* c, const float* d_xyz, uint64_t n, int32_t mode, float min_weight,
+                       float* d_sdf, float* d_weight, float* d_grad, uint8_t* d_valid) {
+    if (!c) return TSDF_EINVAL;
+    int rc = sample_args(c, mode, min_weight);
+    if (rc) return rc;
+    if (n && (!d_xyz || !d_sdf || !d_weight || !d_valid))
+        return fail(c, TSDF_EINVAL, "sample: null buffer");
+    if (!n) return TSDF_OK;
+    rc = drain(c);
+    if (rc) return rc;
+    HIPCHK(c, launch_sample(c->T, c->Pl, c->R, d_xyz, n, mode, min_weight, d_sdf, d_weight, d_grad,
+                            d_valid, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TSDF_OK;
+}
+
+int tsdf_sample(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step, uint32_t xyz_offset,
+                int32_t xyz_is_f64, int32_t mode, float min_weight, float* sdf, float* weight,
+                float* grad, uint8_t* valid) {
+    if (!c) return TSDF_EINVAL;
+    int rc = sample_args(c, mode, min_weight);
+    if (rc) return rc;
+    const uint32_t need = xyz_is_f64 ? 24u : 12u;
+    if (point_step < need || xyz_offset > point_step - need)
+        return fail(c, TSDF_EINVAL, "point_step/xyz_offset inconsistent");
+    if (n && (!pts || !sdf || !weight || !valid)) return fail(c, TSDF_EINVAL, "sample: null buffer");
+    if (!n) return TSDF_OK;
+    rc = drain(c);
+    if (rc) return rc;
+    // pieces of at most max_points: packed fp32 points up, (sdf, weight, grad, valid) down
+    const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(c->max_points, 1));
+    float* d = nullptr;  // xyz (3), sdf, weight, grad (3) per point, then the valid bytes
+    HIPCHK(c, hipMalloc(&d, piece * (8 * sizeof(float) + 1)));
+    float *dx = d, *ds = d + 3 * piece, *dw = d + 4 * piece, *dg = d + 5 * piece;
+    uint8_t* dv = reinterpret_cast<uint8_t*>(d + 8 * piece);
+    std::vector<float> h(3 * piece);
+    const char* base = static_cast<const char*>(pts);
+    hipError_t e = hipSuccess;
+    for (uint64_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
+        const uint64_t m = std::min(piece, n - i0);
+        for (uint64_t i = 0; i < m; i++) {
+            const char* q = base + (i0 + i) * point_step + xyz_offset;
+            if (xyz_is_f64) {
+                double v[3];
+                std::memcpy(v, q, sizeof v);
+                h[3 * i] = (float)v[0];
+                h[3 * i + 1] = (float)v[1];
+                h[3 * i + 2] = (float)v[2];
+            } else {
+                std::memcpy(&h[3 * i], q, 12);
+            }
+        }
+        e = hipMemcpyAsync(dx, h.data(), m * 12, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = launch_sample(c->T, c->Pl, c->R, dx, m, mode, min_weight, ds, dw, grad ? dg : nullptr,
+                              dv, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(sdf + i0, ds, m * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(weight + i0, dw, m * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && grad) e = hipMemcpy(grad + 3 * i0, dg, m * 12, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(valid + i0, dv, m, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(c, TSDF_EHIP, "sample: %s", hipGetErrorString(e));
+    return TSDF_OK;
+}
+
+int tsdf_align_terms_device(tsdf_ctx* c, const float* d_xyz, uint64_t n, const double pose[12],
+                            float min_weight, double out[TSDF_ALIGN_WORDS]) {
+    if (!c) return TSDF_EINVAL;
+    int rc = sample_args(c, TSDF_SAMPLE_TRILINEAR, min_weight);
+    if (rc) return rc;
+    if (!pose || !out || (n && !d_xyz)) return fail(c, TSDF_EINVAL, "align_terms: null argument");
+    std::fill(out, out + TSDF_ALIGN_WORDS, 0.0);
+    if (!n) return TSDF_OK;
+    rc = drain(c);
+    if (rc) return rc;
+    constexpr size_t words = ((size_t)ALIGN_MAX_WG + 1) * ALIGN_PART;
+    if (!c->align_part) HIPCHK(c, hipMalloc(&c->align_part, words * sizeof(double)));
+    OsPose P;
+    for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    HIPCHK(c, launch_align(c->T, c->Pl, c->R, d_xyz, n, P, min_weight, c->align_part, c->stream));
+    double r[29];  // H's upper triangle row-major, b, sum r^2, the valid count
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy(r, c->align_part + (size_t)ALIGN_MAX_WG * ALIGN_PART, sizeof r,
+                        hipMemcpyDeviceToHost));
+    int k = 0;
+    for (int a = 0; a < 6; a++)
+        for (int b = a; b < 6; b++, k++) out[6 * a + b] = out[6 * b + a] = r[k];
+    for (int a = 0; a < 6; a++) out[36 + a] = r[21 + a];
+    out[42] = r[27];
+    out[43] = r[28];
     return TSDF_OK;
 }
 

@@ -457,6 +457,18 @@ hipError_t launch_mesh_count(const Table& T, const Pool& Pl, const Table& H, con
 hipError_t launch_mesh_emit(const Table& T, const Pool& Pl, const Table& H, const Pool& HP,
                             const uint64_t* d_keys, uint32_t nb, float min_weight, int tab,
                             float vs, const uint64_t* d_offsets, float* d_tri, hipStream_t st);
+// sparse map queries (tsdf_sample.hip; include/tsdf_hip_sample.h)
+// mode: TSDF_SAMPLE_NEAREST / TSDF_SAMPLE_TRILINEAR; d_grad may be null; any n (the grid strides)
+hipError_t launch_sample(const Table& T, const Pool& Pl, const RayConst& R, const float* d_xyz,
+                         uint64_t n, int mode, float min_w, float* d_sdf, float* d_w, float* d_grad,
+                         uint8_t* d_valid, hipStream_t st);
+// Gauss-Newton terms of the cloud under pose P: d_part holds (ALIGN_MAX_WG + 1) * ALIGN_PART
+// doubles, the workgroups' partials and, in its last row, their sum in workgroup order: H's upper
+// triangle row-major (21), b (6), sum r^2, the valid count
+constexpr uint32_t ALIGN_MAX_WG = 1024;
+constexpr uint32_t ALIGN_PART = 32;
+hipError_t launch_align(const Table& T, const Pool& Pl, const RayConst& R, const float* d_xyz,
+                        uint64_t n, const OsPose& P, float min_w, double* d_part, hipStream_t st);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, uint64_t n, hipStream_t st);
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, uint64_t n, hipStream_t st);
 

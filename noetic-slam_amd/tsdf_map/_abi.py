@@ -171,12 +171,26 @@ SIGNATURES = {
     "tsdf_os_cartesian_device": (C.c_int, [P, P, C.c_uint64, P, P, C.POINTER(C.c_double), P]),
 }
 
+# include/tsdf_hip_sample.h (TSDF_SAMPLE_API): the sparse map queries of libtsdf_hip.so.  Not part
+# of the tsdf_hip.h contract (the ABI version does not count them; other libraries exporting the
+# C-ABI need not have them): declared on the HIP library only, detected by the symbols' presence.
+SAMPLE_NEAREST = 0
+SAMPLE_TRILINEAR = 1
+SAMPLE_MODES = {"nearest": SAMPLE_NEAREST, "trilinear": SAMPLE_TRILINEAR}
+ALIGN_WORDS = 44  # TSDF_ALIGN_WORDS: H[36] row-major, b[6], sum r^2, n_valid
+SAMPLE_SIGNATURES = {
+    "tsdf_sample_device": (C.c_int, [P, P, C.c_uint64, C.c_int32, C.c_float, P, P, P, P]),
+    "tsdf_sample": (C.c_int, [P, P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32,
+                              C.c_float, FP, FP, FP, C.POINTER(C.c_uint8)]),
+    "tsdf_align_terms_device": (C.c_int, [P, P, C.c_uint64, D3, C.c_float, D3]),
+}
 
-def declare(lib, names=None, optional=()):
+
+def declare(lib, names=None, optional=(), table=None):
     """Attach restype/argtypes for the ABI symbols present in `lib`; raise if a required one is
-    missing."""
+    missing.  table: the signature table (default SIGNATURES, the tsdf_hip.h contract)."""
     missing = []
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in (SIGNATURES if table is None else table).items():
         if names is not None and name not in names:
             continue
         fn = getattr(lib, name, None)

@@ -32,6 +32,8 @@ def load_hip_library(path=None):
     except ImportError:
         pass
     lib = _abi.declare(ctypes.CDLL(p))
+    # the sparse map queries (include/tsdf_hip_sample.h): part of this library, not of the ABI
+    _abi.declare(lib, table=_abi.SAMPLE_SIGNATURES)
     if lib.tsdf_abi_version() != ABI_VERSION:
         raise RuntimeError("libtsdf_hip.so ABI version mismatch")
     if path is None:

@@ -232,6 +232,61 @@ class TSDFVolume:
                                                w.ctypes.data_as(_abi.FP)), "query_dense")
         return s, w
 
+    def _sample_fn(self, name):
+        """An entry point of include/tsdf_hip_sample.h; a library without it (the feature is
+        detected by the symbol) cannot sample, and says so."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (sparse map queries are part of "
+                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    def sample(self, points, mode="trilinear", min_weight=0.0):
+        """The field at world points (N, 3) float32 / float64 (float64 is rounded to float32):
+        (sdf (N,), weight (N,), grad (N, 3), valid (N,) bool).  mode "nearest": the voxel holding
+        the point, grad 0.  mode "trilinear": the interpolant of the 8 voxel centres around it and
+        its analytic gradient (metres per metre), valid where all 8 are observed with weight >=
+        min_weight; elsewhere (background, 0, 0).  include/tsdf_hip_sample.h states the arithmetic."""
+        if mode not in _abi.SAMPLE_MODES:
+            raise ValueError("mode must be one of %s" % sorted(_abi.SAMPLE_MODES))
+        fn = self._sample_fn("tsdf_sample")
+        pts = np.asarray(points)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise ValueError("points must be np.ndarray(n, 3)")
+        if pts.dtype not in (np.float32, np.float64):
+            raise TypeError("points dtype must be np.float32 or np.float64")
+        pts = np.ascontiguousarray(pts)
+        is64 = pts.dtype == np.float64
+        n = pts.shape[0]
+        s = np.empty(n, np.float32)
+        w = np.empty(n, np.float32)
+        g = np.empty((n, 3), np.float32)
+        v = np.empty(n, np.uint8)
+        self._check(fn(self._ctx, pts.ctypes.data_as(C.c_void_p), n, 24 if is64 else 12, 0,
+                       1 if is64 else 0, _abi.SAMPLE_MODES[mode], float(min_weight),
+                       s.ctypes.data_as(_abi.FP), w.ctypes.data_as(_abi.FP),
+                       g.ctypes.data_as(_abi.FP), v.ctypes.data_as(C.POINTER(C.c_uint8))), "sample")
+        return s, w, g, v.astype(bool)
+
+    def sample_cloud(self, data, n, point_step, xyz_offset, mode="trilinear", min_weight=0.0,
+                     xyz_is_f64=False):
+        """`sample` on PointCloud2-style raw records (e.g. dlio::Point, point_step 32)."""
+        fn = self._sample_fn("tsdf_sample")
+        buf = np.frombuffer(data, dtype=np.uint8)
+        if buf.size < n * point_step:
+            raise ValueError("buffer smaller than n * point_step")
+        n = int(n)
+        s = np.empty(n, np.float32)
+        w = np.empty(n, np.float32)
+        g = np.empty((n, 3), np.float32)
+        v = np.empty(n, np.uint8)
+        self._check(fn(self._ctx, buf.ctypes.data_as(C.c_void_p), n, int(point_step),
+                       int(xyz_offset), 1 if xyz_is_f64 else 0, _abi.SAMPLE_MODES[mode],
+                       float(min_weight), s.ctypes.data_as(_abi.FP), w.ctypes.data_as(_abi.FP),
+                       g.ctypes.data_as(_abi.FP), v.ctypes.data_as(C.POINTER(C.c_uint8))),
+                    "sample_cloud")
+        return s, w, g, v.astype(bool)
+
     def extract_triangle_mesh(self, fill_holes=True, min_weight=0.0, table="generated",
                               halo=None):
         """VDBVolume.extract_triangle_mesh: (vertices (3T, 3) float32, triangles (T, 3) int64) —
@@ -496,6 +551,49 @@ class HipTSDFVolume(TSDFVolume):
             raise ValueError("scan_offsets must have n_scans + 1 entries")
         self._check(fn(self._ctx, C.c_void_p(int(d_xyz_ptr)), offs.ctypes.data_as(_abi.U64P),
                        org.shape[0], org.ctypes.data_as(_abi.D3)), "integrate_batch_device")
+
+    def sample_device(self, d_xyz_ptr, n, d_sdf_ptr, d_weight_ptr, d_grad_ptr, d_valid_ptr,
+                      mode="trilinear", min_weight=0.0):
+        """`sample` for n device points (n x 3 float32) into caller-given device buffers: sdf and
+        weight (n float32), grad (3 n float32, or None / 0 to skip it), valid (n uint8).  The
+        points must be complete before the call; the outputs are complete when it returns."""
+        if mode not in _abi.SAMPLE_MODES:
+            raise ValueError("mode must be one of %s" % sorted(_abi.SAMPLE_MODES))
+        fn = self._sample_fn("tsdf_sample_device")
+        self._check(fn(self._ctx, C.c_void_p(int(d_xyz_ptr or 0)), int(n), _abi.SAMPLE_MODES[mode],
+                       float(min_weight), C.c_void_p(int(d_sdf_ptr or 0)),
+                       C.c_void_p(int(d_weight_ptr or 0)), C.c_void_p(int(d_grad_ptr or 0)),
+                       C.c_void_p(int(d_valid_ptr or 0))), "sample_device")
+
+    def align_terms(self, points, pose, min_weight=0.0, n=None):
+        """Gauss-Newton terms of the point-to-TSDF error of a cloud under `pose` (3x4 or 4x4, world
+        from cloud): (H (6, 6), b (6,), e = sum r^2, n_valid) over the points whose trilinear sample
+        is valid, r the sampled distance and J = [g, q x g] for a left perturbation (dt, dtheta).
+        points: an (N, 3) array (copied to the device), or a device pointer with n points of
+        float32 xyz.  The same inputs give the same bits on every call."""
+        fn = self._sample_fn("tsdf_align_terms_device")
+        T = np.asarray(pose, np.float64)
+        if T.shape == (4, 4):
+            T = T[:3]
+        if T.shape != (3, 4):
+            raise ValueError("pose must be a (3, 4) or (4, 4) matrix")
+        T = np.ascontiguousarray(T)
+        keep = None
+        if isinstance(points, (int, np.integer)):
+            if n is None:
+                raise ValueError("a device pointer needs n")
+            ptr = int(points)
+        else:
+            import torch
+            pts = np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))
+            keep = torch.from_numpy(pts).to(self.tensor_device)
+            torch.cuda.synchronize(keep.device)
+            ptr, n = keep.data_ptr(), pts.shape[0]
+        out = np.empty(_abi.ALIGN_WORDS, np.float64)
+        self._check(fn(self._ctx, C.c_void_p(ptr), int(n), _d3(T), float(min_weight), _d3(out)),
+                    "align_terms")
+        del keep
+        return out[:36].reshape(6, 6).copy(), out[36:42].copy(), float(out[42]), int(out[43])
 
     def set_profiling(self, on=True):
         self._check(self._lib.tsdf_set_profiling(self._ctx, 1 if on else 0), "set_profiling")
