@@ -286,6 +286,22 @@ int tsdf_integrate_batch_device_pose(tsdf_ctx* ctx, const float* d_xyz,
  * TSDF_ENOMEM. */
 int tsdf_sync(tsdf_ctx* ctx);
 
+/* Index domain (integrate side; tests/test_domain_edge.py).  The map holds voxels |i| < 2^23 on
+ * every axis (419 km from the frame's zero at 5 cm voxels).
+ *   - Integrate never writes a voxel outside the domain: a ray that leaves it, or lies outside it,
+ *     is walked as usual and its samples outside are dropped one by one; the ray still counts in
+ *     tsdf_stats.n_rays_total.
+ *   - Far rays: a ray is dropped whole, like a range-filtered one (not in n_rays_total), when an
+ *     index-space coordinate of its walk's start -- for TSDF_SEM_VOXBLOX of its start, its end or
+ *     its hit point -- is not finite or has magnitude >= 2^30, or when its length or band end is not
+ *     finite.  This is decided on the floats, before any float -> int conversion.  2^30 leaves room
+ *     for the walk's 2^20 steps without integer overflow and lies outside every band of a ray that
+ *     touches the domain, so no voxel of the domain is affected.  NaN and +-inf coordinates fall
+ *     under the rule whatever max_range is.
+ *   - A ray is walked for at most 2^20 voxels (carving over longer distances stops there).
+ *   - TSDF_VB_MERGED drops the points whose voxel floor(p / vs + 1e-6) lies outside |i| < 2^20 on an
+ *     axis before bundling (its bundling keys hold 21 bits per axis: 52 km at 5 cm voxels). */
+
 /* Dense read-out of voxels lo..hi-1 (voxel index coordinates, voxel i spans [i*vs, (i+1)*vs)),
  * x fastest: out[((z-lo2)*(hi1-lo1) + (y-lo1))*(hi0-lo0) + (x-lo0)].  Unobserved voxels, and
  * voxels outside the map's index domain (|i| >= 2^23 per axis), read (sdf_trunc, 0) — VDBFusion's

@@ -12,6 +12,25 @@ namespace tsdf {
 // ------------------------------------------------------------------------------------------------
 // ray setup and walk (same op order as oracle/tsdf_oracle.c walk_ray)
 
+// The far-ray rule (include/tsdf_hip.h "Index domain"; the oracle's far_ok): a ray is dropped whole,
+// like a range-filtered one, unless every index-space coordinate handed to a float -> int
+// conversion is finite and of magnitude < 2^30.  Decided on the floats, before the conversion
+// (out-of-range conversions differ between targets); 2^30 leaves MAX_DDA_STEPS steps without int
+// overflow and lies far outside the domain's bands, so no ray that touches |i| < 2^23 is affected.
+constexpr float FAR_LIMIT = 1073741824.0f;  // 2^30
+
+__device__ __forceinline__ bool far_ok(float x, float y, float z) {
+    return __builtin_fabsf(x) < FAR_LIMIT && __builtin_fabsf(y) < FAR_LIMIT &&
+           __builtin_fabsf(z) < FAR_LIMIT;  // false for NaN
+}
+
+// A walk's wave skips the per-voxel domain check when every lane's start voxel lies more than the
+// band's length inside |index| < VOX_LIMIT (two-sided compares: defined for any int).
+__device__ __forceinline__ bool start_inside(int vx, int vy, int vz, int band_vox) {
+    const int lim = VOX_LIMIT - band_vox;
+    return vx > -lim && vx < lim && vy > -lim && vy < lim && vz > -lim && vz < lim;
+}
+
 struct RayState {
     float px, py, pz;  // hit point (world)
     float t1i;         // band end (index units)
@@ -40,7 +59,8 @@ __device__ __forceinline__ void axis_init(float u, float s, float t0i, int v, fl
     }
 }
 
-// Returns false when the ray is filtered out (zero/NaN length, outside [min_range, max_range]).
+// Returns false when the ray is filtered out (zero/NaN length, outside [min_range, max_range], or
+// the far-ray rule: start or band end not finite, start beyond 2^30).
 __device__ __forceinline__ bool ray_init(const RayConst& R, float ox, float oy, float oz, float px,
                                          float py, float pz, RayState& r) {
     const float dx = px - ox, dy = py - oy, dz = pz - oz;
@@ -56,6 +76,7 @@ __device__ __forceinline__ bool ray_init(const RayConst& R, float ox, float oy, 
     const float sx = ox * R.inv_vs + ux * t0i;
     const float sy = oy * R.inv_vs + uy * t0i;
     const float sz = oz * R.inv_vs + uz * t0i;
+    if (!far_ok(sx, sy, sz) || !(r.t1i < __builtin_inff())) return false;
     r.vx = (int)__builtin_floorf(sx);
     r.vy = (int)__builtin_floorf(sy);
     r.vz = (int)__builtin_floorf(sz);
@@ -228,7 +249,9 @@ __device__ __forceinline__ void vb_axis(float ss, float es, int& v, int& st, flo
                                         int& steps) {
     v = (int)__builtin_floorf(ss + 1e-6f);  // getGridIndexFromPoint: floor(x + kCoordinateEpsilon)
     const int e = (int)__builtin_floorf(es + 1e-6f);
-    steps += e > v ? e - v : v - e;
+    // |e - v| < 2^31 (far-ray rule), clamped per axis so that the three-axis sum cannot overflow
+    const uint32_t d = e > v ? (uint32_t)e - (uint32_t)v : (uint32_t)v - (uint32_t)e;
+    steps += (int)min(d, (uint32_t)MAX_DDA_STEPS);
     const float r = es - ss;
     st = (0.0f < r) - (r < 0.0f);
     const float corr = st > 0 ? 1.0f : 0.0f;
@@ -283,10 +306,16 @@ __device__ __forceinline__ bool vb_init(const RayConst& R, const BatchRef& D, ui
         sy = oy;
         sz = oz;
     }
+    // the far-ray rule, on the hit point as well: a far point makes no clearing ray either
+    const float ssx = sx * R.inv_vs, ssy = sy * R.inv_vs, ssz = sz * R.inv_vs;
+    const float esx = ex * R.inv_vs, esy = ey * R.inv_vs, esz = ez * R.inv_vs;
+    if (!far_ok(ssx, ssy, ssz) || !far_ok(esx, esy, esz) ||
+        !far_ok(px * R.inv_vs, py * R.inv_vs, pz * R.inv_vs) || !(depth < __builtin_inff()))
+        return false;
     int steps = 0;
-    vb_axis(sx * R.inv_vs, ex * R.inv_vs, r.vx, r.sx, r.tnx, r.tdx, steps);
-    vb_axis(sy * R.inv_vs, ey * R.inv_vs, r.vy, r.sy, r.tny, r.tdy, steps);
-    vb_axis(sz * R.inv_vs, ez * R.inv_vs, r.vz, r.sz, r.tnz, r.tdz, steps);
+    vb_axis(ssx, esx, r.vx, r.sx, r.tnx, r.tdx, steps);
+    vb_axis(ssy, esy, r.vy, r.sy, r.tny, r.tdy, steps);
+    vb_axis(ssz, esz, r.vz, r.sz, r.tnz, r.tdz, steps);
     r.rem = min(steps, MAX_DDA_STEPS - 1);
     // TsdfIntegratorBase::getVoxelWeight: 1 / z^2 of the point's sensor-frame depth z (the scan's
     // z axis dotted with p - o, Eigen's x + (y + z)); |z| <= kEpsilon (1e-6) gives 0.  The weight
@@ -403,8 +432,7 @@ struct Walk<0> {  // TSDF_SEM_VDBFUSION
     }
     // the ray's voxels all lie inside |index| < VOX_LIMIT (so the per-voxel check can go)
     __device__ static __forceinline__ bool inside(const RayConst& R, const State& r) {
-        const int m = max(max(abs(r.vx), abs(r.vy)), abs(r.vz));
-        return m < VOX_LIMIT - R.band_vox;
+        return start_inside(r.vx, r.vy, r.vz, R.band_vox);
     }
     __device__ static __forceinline__ bool step(State& r) { return ray_step(r); }
     __device__ static __forceinline__ bool step_sel(State& r) { return ray_step_sel(r); }
@@ -437,8 +465,7 @@ struct Walk<1> {  // TSDF_SEM_VOXBLOX
         return vb_sample(R, ox, oy, oz, r, s, check);
     }
     __device__ static __forceinline__ bool inside(const RayConst& R, const State& r) {
-        const int m = max(max(abs(r.vx), abs(r.vy)), abs(r.vz));
-        return m < VOX_LIMIT - R.band_vox;
+        return start_inside(r.vx, r.vy, r.vz, R.band_vox);
     }
     __device__ static __forceinline__ bool step(State& r) { return vb_step(r); }
     __device__ static __forceinline__ bool step_sel(State& r) { return vb_step_sel(r); }
@@ -538,6 +565,7 @@ __device__ __forceinline__ bool vdb_init(const RayConst& R, const BatchRef& D, u
     r.t1i = L * t1;
     // math::DDA::init
     const float qx = ex + dix * t0i, qy = ey + diy * t0i, qz = ez + diz * t0i;
+    if (!far_ok(qx, qy, qz) || !(r.t1i < __builtin_inff())) return false;  // the far-ray rule
     r.vx = (int)__builtin_floorf(qx);
     r.vy = (int)__builtin_floorf(qy);
     r.vz = (int)__builtin_floorf(qz);
@@ -732,8 +760,7 @@ struct Walk<2> {  // TSDF_SEM_VDBFUSION_F64
         return inl && (proj > 0.0 || proj < 0.0) && sdf > -R.tau;
     }
     __device__ static __forceinline__ bool inside(const RayConst& R, const State& r) {
-        const int m = max(max(abs(r.vx), abs(r.vy)), abs(r.vz));
-        return m < VOX_LIMIT - R.band_vox;
+        return start_inside(r.vx, r.vy, r.vz, R.band_vox);
     }
     __device__ static __forceinline__ bool step(State& r) { return ray_step(r); }
     __device__ static __forceinline__ bool step_sel(State& r) { return ray_step_sel(r); }

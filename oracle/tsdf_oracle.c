@@ -322,8 +322,19 @@ int tsdf_oracle_set_mode(tsdf_ctx* c, int mode) {
 typedef void (*visit_fn)(tsdf_ctx* c, int32_t vx, int32_t vy, int32_t vz, float s, float w,
                          void* user);
 
-/* Returns the number of voxels visited by the DDA (gated or not); calls visit() for every voxel
- * with sdf > -tau, in DDA order.  All arithmetic fp32, no contraction (built -ffp-contract=off). */
+/* The far-ray rule (include/tsdf_hip.h "Index domain"; the kernels' far_ok): a ray is dropped whole,
+ * like a range-filtered one, unless every index-space coordinate handed to a float -> int
+ * conversion is finite and of magnitude < 2^30.  Decided on the floats, before the conversion (an
+ * out-of-range conversion is undefined in C and differs between targets); 2^30 leaves MAX_DDA_STEPS
+ * steps without int overflow and lies far outside the domain's bands. */
+#define FAR_LIMIT 1073741824.0f /* 2^30 */
+
+static int far_ok(float x, float y, float z) {
+    return fabsf(x) < FAR_LIMIT && fabsf(y) < FAR_LIMIT && fabsf(z) < FAR_LIMIT; /* false for NaN */
+}
+
+/* Returns the number of voxels visited by the DDA (gated or not), -1 for a dropped ray; calls
+ * visit() for every voxel with sdf > -tau, in DDA order.  All arithmetic fp32, no contraction (built -ffp-contract=off). */
 static int64_t walk_ray(tsdf_ctx* c, float px, float py, float pz, float ox, float oy, float oz,
                         visit_fn visit, void* user) {
     const float vs = c->vs, inv_vs = c->inv_vs, tau = c->tau;
@@ -342,6 +353,7 @@ static int64_t walk_ray(tsdf_ctx* c, float px, float py, float pz, float ox, flo
     const float sx = ox * inv_vs + ux * t0i;
     const float sy = oy * inv_vs + uy * t0i;
     const float sz = oz * inv_vs + uz * t0i;
+    if (!far_ok(sx, sy, sz) || !(t1i < INFINITY)) return -1; /* the far-ray rule */
     int32_t v[3] = {(int32_t)floorf(sx), (int32_t)floorf(sy), (int32_t)floorf(sz)};
     const float s3[3] = {sx, sy, sz}, u3[3] = {ux, uy, uz};
     float tn[3], td[3];
@@ -438,10 +450,9 @@ static int64_t walk_ray_vdb(tsdf_ctx* c, const double p[3], const double o[3], v
     const float t0_i = L * t0, t1_i = L * t1;
     int32_t v[3], st[3];
     float tn[3], td[3];
-    for (int a = 0; a < 3; a++) {
-        pos[a] = eye_i[a] + dir_i[a] * t0_i;
-        v[a] = (int32_t)floorf(pos[a]);
-    }
+    for (int a = 0; a < 3; a++) pos[a] = eye_i[a] + dir_i[a] * t0_i;
+    if (!far_ok(pos[0], pos[1], pos[2]) || !(t1_i < INFINITY)) return -1; /* the far-ray rule */
+    for (int a = 0; a < 3; a++) v[a] = (int32_t)floorf(pos[a]);
     for (int a = 0; a < 3; a++) {
         if (dir_i[a] == 0.0f) {
             st[a] = 0;
@@ -476,7 +487,7 @@ static int64_t walk_ray_vdb(tsdf_ctx* c, const double p[3], const double o[3], v
         int a; /* math::MinIndex */
         if (tn[0] < tn[1] && tn[0] < tn[2]) a = 0;
         else a = (tn[1] < tn[2]) ? 1 : 2;
-        if (tn[a] > t1_i) break;
+        if (!(tn[a] <= t1_i)) break; /* a NaN entry time ends the walk, as the kernels' ray_step */
         v[a] += st[a];
         tn[a] += td[a];
     }
@@ -567,6 +578,10 @@ static int64_t walk_ray_vb(tsdf_ctx* c, float px, float py, float pz, float ox, 
     }
     const float ss[3] = {sx * inv_vs, sy * inv_vs, sz * inv_vs};
     const float es[3] = {ex * inv_vs, ey * inv_vs, ez * inv_vs};
+    /* the far-ray rule, on the hit point as well: a far point makes no clearing ray either */
+    if (!far_ok(ss[0], ss[1], ss[2]) || !far_ok(es[0], es[1], es[2]) ||
+        !far_ok(px * inv_vs, py * inv_vs, pz * inv_vs) || !(depth < INFINITY))
+        return -1;
     int32_t v[3], st[3];
     float tn[3], td[3];
     int64_t steps = 0;
@@ -585,7 +600,8 @@ static int64_t walk_ray_vb(tsdf_ctx* c, float px, float py, float pz, float ox, 
             td[a] = (float)st[a] / r;
         }
     }
-    if (steps > MAX_DDA_STEPS) steps = MAX_DDA_STEPS;
+    /* at most MAX_DDA_STEPS voxels, as the other walks (the kernels' vb_init: rem) */
+    if (steps > MAX_DDA_STEPS - 1) steps = MAX_DDA_STEPS - 1;
     for (int64_t k = 0;; k++) {
         if (v[0] > -VOX_LIMIT && v[0] < VOX_LIMIT && v[1] > -VOX_LIMIT && v[1] < VOX_LIMIT &&
             v[2] > -VOX_LIMIT && v[2] < VOX_LIMIT) {

@@ -6,6 +6,9 @@
  *     the sequential and VDB-literal modes, Voxblox merged bundling, space carving;
  *   - the exact fixed-point sums at their extremes: Voxblox 1/z^2 weights capped at 2^16 on
  *     thousands of points in one voxel, points on voxel faces, far coordinates;
+ *   - far and non-finite points (the far-ray rule of include/tsdf_hip.h "Index domain": no
+ *     out-of-range float -> int conversion, -fsanitize=float-cast-overflow), whose field and ray
+ *     count must be those of the ordinary points alone;
  *   - import / export / query, marching cubes (every table), the border-reduce transaction
  *     (commit and abort), the one-process sharded calls and the sharded mesh.
  * Input: argv[1], scans as u64 n_scans, then per scan u64 n, f64 origin[3], f32 xyz[3 n].
@@ -136,6 +139,64 @@ static void extremes(void) {
         tsdf_destroy(v);
     }
     free(xyz);
+}
+
+/* ~200 ordinary points of a scan mixed with far (>= 2^30 voxels on an axis) and non-finite ones:
+ * every semantics, max_range inf and 30 (Voxblox: clearing rays), Merged bundling and carving.
+ * The far points are dropped whole, so the field and the ray count are the ordinary points'. */
+static void far_points(const scan_t* sc) {
+    const float big0 = 53687091.2f * (1.0f + 1.0f / 1048576.0f); /* 2^30 voxels of 5 cm, and a bit */
+    const float mags[8] = {big0, 2e8f, 1e20f, 1e30f, 3e38f, INFINITY, NAN, 1.8e19f};
+    enum { NORD = 200, NFAR = 8 * 10 };
+    float* ord = (float*)malloc(NORD * 12);
+    float* mix = (float*)malloc((NORD + NFAR) * 12);
+    const uint64_t stride = sc->n / NORD;
+    int nm = 0;
+    for (int i = 0; i < NORD; i++) {
+        memcpy(ord + 3 * i, sc->xyz + 3 * (uint64_t)i * stride, 12);
+        memcpy(mix + 3 * nm++, ord + 3 * i, 12);
+        if (i % 5 == 0 && i / 5 < 8 * 5) { /* two far points after every fifth ordinary one */
+            const float m = mags[(i / 5) % 8];
+            const int a = (i / 40) % 3;
+            for (int sgn = 0; sgn < 2; sgn++) {
+                float q[3] = {1.5f, -2.5f, 0.5f};
+                q[a] = sgn ? -m : m;
+                if (i / 5 >= 24) { q[(a + 1) % 3] = m; q[(a + 2) % 3] = sgn ? m : -m; }
+                memcpy(mix + 3 * nm++, q, 12);
+            }
+        }
+    }
+    double q[7];
+    pose_of(sc, 1, q);
+    static const struct { int sem; double max_range; int carving, merged, threads; } cfgs[12] = {
+        {0, INFINITY, 0, 0, 1}, {1, INFINITY, 0, 0, 1}, {2, INFINITY, 0, 0, 1},
+        {0, 30.0, 0, 0, 1},     {1, 30.0, 0, 0, 1},     {2, 30.0, 0, 0, 1},
+        {0, 30.0, 1, 0, 1},     {1, 30.0, 1, 0, 1},     {2, 30.0, 1, 0, 1},
+        {1, INFINITY, 0, 1, 1}, {1, 30.0, 0, 1, 1},     {2, INFINITY, 0, 0, 3}};
+    for (int cfg = 0; cfg < 12; cfg++) {
+        tsdf_params p = params(cfgs[cfg].sem);
+        p.max_range = cfgs[cfg].max_range;
+        p.space_carving = cfgs[cfg].carving;
+        if (cfgs[cfg].merged) p.voxblox_method = TSDF_VB_MERGED;
+        tsdf_ctx* a = make(&p);
+        tsdf_ctx* b = make(&p);
+        OK(tsdf_oracle_set_threads(a, cfgs[cfg].threads));
+        OK(tsdf_integrate_pose(a, mix, (uint64_t)nm, 12, 0, 0, q));
+        OK(tsdf_integrate_pose(b, ord, NORD, 12, 0, 0, q));
+        field_t fa = field(a), fb = field(b);
+        tsdf_stats sa, sb;
+        OK(tsdf_get_stats(a, &sa));
+        OK(tsdf_get_stats(b, &sb));
+        CHECK(fa.n > 100 && same(fa, fb), "far points changed the field (cfg %d): %llu %llu", cfg,
+              (unsigned long long)fa.n, (unsigned long long)fb.n);
+        CHECK(sa.n_rays_total == sb.n_rays_total, "far points were counted as rays (cfg %d): %llu %llu",
+              cfg, (unsigned long long)sa.n_rays_total, (unsigned long long)sb.n_rays_total);
+        drop(fa); drop(fb);
+        tsdf_destroy(a);
+        tsdf_destroy(b);
+    }
+    free(ord);
+    free(mix);
 }
 
 static void readout(const scan_t* sc) {
@@ -269,6 +330,7 @@ int main(int argc, char** argv) {
         modes(sc, (int)ns, TSDF_SEM_VOXBLOX, TSDF_VB_MERGED, 0, threads);
         modes(sc, 1, TSDF_SEM_VDBFUSION, TSDF_VB_SIMPLE, 1, threads);
         extremes();
+        far_points(sc);
         readout(sc);
         sharded(sc, (int)ns);
     }

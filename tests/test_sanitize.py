@@ -4,7 +4,9 @@ with ThreadSanitizer (oracle/Makefile `sanitize`), driven through its whole C-AB
 tests/cpp/oracle_sanitize.c on real scans: every semantics in serial and in the partitioned
 multi-threaded scan-fused mode (bit for bit), Voxblox's capped 1/z^2 weights on thousands of
 points in one voxel (the exact int64 fixed-point sums at their extremes, where ADVICE r3 found an
-overflow), rays onto voxel faces and far from the origin, read-out, marching cubes, the
+overflow), rays onto voxel faces and far from the origin, far and non-finite points (with
+-fsanitize=float-cast-overflow: the far-ray rule leaves no out-of-range float -> int conversion),
+read-out, marching cubes, the
 border-reduce transaction (commit and abort), the sharded calls and the sharded mesh.  Host code
 only: GPU sanitizers are not available on this pool."""
 import os
