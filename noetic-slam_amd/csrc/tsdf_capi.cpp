@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/tsdf_hip.h"
+#include "../../include/tsdf_hip_raycast.h"
 #include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
 #include "pack_pool.h"
@@ -2301,6 +2302,107 @@ int tsdf_align_terms_device(tsdf_ctx* c, const float* d_xyz, uint64_t n, const d
     for (int a = 0; a < 6; a++) out[36 + a] = r[21 + a];
     out[42] = r[27];
     out[43] = r[28];
+    return TSDF_OK;
+}
+
+// ---- raycast (include/tsdf_hip_raycast.h) -------------------------------------------------------
+
+// The number of lattice samples: the k with t_min + (float)k * step <= t_max, in the kernel's fp32
+// expression.  Every step of it is monotone in k, so the k that pass form a prefix and a bisection
+// counts them; the count is capped at RAYCAST_MAX_SAMPLES.
+static uint32_t raycast_samples(float t_min, float t_max, float step) {
+    const auto in = [&](uint32_t k) {
+        const float t = t_min + (float)k * step;
+        return t <= t_max;
+    };
+    if (!in(0)) return 0;
+    uint32_t lo = 0, hi = RAYCAST_MAX_SAMPLES;  // in(lo); hi is past the cap
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (in(mid)) lo = mid;
+        else hi = mid;
+    }
+    return lo + 1;
+}
+
+// the argument rules both raycast entry points share (the buffers apart)
+static int raycast_args(tsdf_ctx* c, float t_min, float t_max, float step, int32_t mode,
+                        float min_weight) {
+    if (mode != TSDF_SAMPLE_NEAREST && mode != TSDF_SAMPLE_TRILINEAR)
+        return fail(c, TSDF_EINVAL, "raycast: mode must be TSDF_SAMPLE_NEAREST or _TRILINEAR");
+    if (!(min_weight >= 0.0f)) return fail(c, TSDF_EINVAL, "raycast: min_weight is negative or NaN");
+    if (!std::isfinite(t_min) || !std::isfinite(t_max) || !std::isfinite(step))
+        return fail(c, TSDF_EINVAL, "raycast: t_min, t_max and step must be finite");
+    if (!(step > 0.0f)) return fail(c, TSDF_EINVAL, "raycast: step must be positive");
+    if (t_min < 0.0f || t_max < t_min)
+        return fail(c, TSDF_EINVAL, "raycast: need 0 <= t_min <= t_max");
+    if (((double)t_max - (double)t_min) / (double)step >= (double)RAYCAST_MAX_SAMPLES)
+        return fail(c, TSDF_EINVAL, "raycast: (t_max - t_min) / step must stay below 2^20 samples");
+    if (c->p.n_sectors > 1)
+        return fail(c, TSDF_EINVAL, "raycast: the context holds one sector shard of the map "
+                                    "(n_sectors > 1); raycasting a sharded field is not supported");
+    if (border_busy(c)) return TSDF_EINVAL;
+    return TSDF_OK;
+}
+
+int tsdf_raycast_device(tsdf_ctx* c, const float* d_org, const float* d_dir, uint64_t n,
+                        const double pose[12], float t_min, float t_max, float step, int32_t mode,
+                        float min_weight, float* d_depth, float* d_normal, uint8_t* d_hit) {
+    if (!c) return TSDF_EINVAL;
+    int rc = raycast_args(c, t_min, t_max, step, mode, min_weight);
+    if (rc) return rc;
+    if (n && (!d_org || !d_dir || !d_depth || !d_hit))
+        return fail(c, TSDF_EINVAL, "raycast: null buffer");
+    if (!n) return TSDF_OK;
+    rc = drain(c);
+    if (rc) return rc;
+    OsPose P;
+    if (pose)
+        for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    HIPCHK(c, launch_raycast(c->T, c->Pl, c->R, d_org, d_dir, n, pose ? &P : nullptr, t_min, step,
+                             raycast_samples(t_min, t_max, step), mode, min_weight, d_depth,
+                             d_normal, d_hit, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TSDF_OK;
+}
+
+int tsdf_raycast(tsdf_ctx* c, const float* org, const float* dir, uint64_t n, const double pose[12],
+                 float t_min, float t_max, float step, int32_t mode, float min_weight, float* depth,
+                 float* normal, uint8_t* hit) {
+    if (!c) return TSDF_EINVAL;
+    int rc = raycast_args(c, t_min, t_max, step, mode, min_weight);
+    if (rc) return rc;
+    if (n && (!org || !dir || !depth || !hit)) return fail(c, TSDF_EINVAL, "raycast: null buffer");
+    if (!n) return TSDF_OK;
+    rc = drain(c);
+    if (rc) return rc;
+    OsPose P;
+    if (pose)
+        for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    const uint32_t n_k = raycast_samples(t_min, t_max, step);
+    // pieces of at most max_points: (origin, direction) up, (depth, normal, hit) down
+    const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(c->max_points, 1));
+    float* d = nullptr;  // org (3), dir (3), depth, normal (3) per ray, then the hit bytes
+    HIPCHK(c, hipMalloc(&d, piece * (10 * sizeof(float) + 1)));
+    float *dorg = d, *ddir = d + 3 * piece, *dd = d + 6 * piece, *dn = d + 7 * piece;
+    uint8_t* dh = reinterpret_cast<uint8_t*>(d + 10 * piece);
+    hipError_t e = hipSuccess;
+    for (uint64_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
+        const uint64_t m = std::min(piece, n - i0);
+        e = hipMemcpyAsync(dorg, org + 3 * i0, m * 12, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(ddir, dir + 3 * i0, m * 12, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess)
+            e = launch_raycast(c->T, c->Pl, c->R, dorg, ddir, m, pose ? &P : nullptr, t_min, step,
+                               n_k, mode, min_weight, dd, normal ? dn : nullptr, dh, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(depth + i0, dd, m * 4, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && normal)
+            e = hipMemcpy(normal + 3 * i0, dn, m * 12, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(hit + i0, dh, m, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(c, TSDF_EHIP, "raycast: %s", hipGetErrorString(e));
     return TSDF_OK;
 }
 

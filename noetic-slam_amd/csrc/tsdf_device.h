@@ -469,6 +469,14 @@ constexpr uint32_t ALIGN_MAX_WG = 1024;
 constexpr uint32_t ALIGN_PART = 32;
 hipError_t launch_align(const Table& T, const Pool& Pl, const RayConst& R, const float* d_xyz,
                         uint64_t n, const OsPose& P, float min_w, double* d_part, hipStream_t st);
+// raycast (tsdf_raycast.hip; include/tsdf_hip_raycast.h): depth, normal (d_normal may be null) and a
+// hit flag per ray; P null: rays as given.  n_k: the lattice's sample count (the k with
+// t_min + (float)k * step <= t_max), at most RAYCAST_MAX_SAMPLES; any n (the grid strides)
+constexpr uint32_t RAYCAST_MAX_SAMPLES = (uint32_t)MAX_DDA_STEPS;
+hipError_t launch_raycast(const Table& T, const Pool& Pl, const RayConst& R, const float* d_org,
+                          const float* d_dir, uint64_t n, const OsPose* P, float t_min, float step,
+                          uint32_t n_k, int mode, float min_w, float* d_depth, float* d_normal,
+                          uint8_t* d_hit, hipStream_t st);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, uint64_t n, hipStream_t st);
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, uint64_t n, hipStream_t st);
 

@@ -185,6 +185,16 @@ SAMPLE_SIGNATURES = {
     "tsdf_align_terms_device": (C.c_int, [P, P, C.c_uint64, D3, C.c_float, D3]),
 }
 
+# include/tsdf_hip_raycast.h (TSDF_RAYCAST_API): raycasting the map, likewise a feature of
+# libtsdf_hip.so outside the contract, declared on the HIP library only.  Modes: SAMPLE_MODES.
+U8P = C.POINTER(C.c_uint8)
+RAYCAST_SIGNATURES = {
+    "tsdf_raycast_device": (C.c_int, [P, P, P, C.c_uint64, D3, C.c_float, C.c_float, C.c_float,
+                                      C.c_int32, C.c_float, P, P, P]),
+    "tsdf_raycast": (C.c_int, [P, FP, FP, C.c_uint64, D3, C.c_float, C.c_float, C.c_float,
+                               C.c_int32, C.c_float, FP, FP, U8P]),
+}
+
 
 def declare(lib, names=None, optional=(), table=None):
     """Attach restype/argtypes for the ABI symbols present in `lib`; raise if a required one is

@@ -34,6 +34,8 @@ def load_hip_library(path=None):
     lib = _abi.declare(ctypes.CDLL(p))
     # the sparse map queries (include/tsdf_hip_sample.h): part of this library, not of the ABI
     _abi.declare(lib, table=_abi.SAMPLE_SIGNATURES)
+    # ... and the raycast (include/tsdf_hip_raycast.h)
+    _abi.declare(lib, table=_abi.RAYCAST_SIGNATURES)
     if lib.tsdf_abi_version() != ABI_VERSION:
         raise RuntimeError("libtsdf_hip.so ABI version mismatch")
     if path is None:

@@ -237,8 +237,8 @@ class TSDFVolume:
         detected by the symbol) cannot sample, and says so."""
         fn = getattr(self._lib, name, None)
         if fn is None or fn.argtypes is None:
-            raise NotImplementedError("%s does not export %s (sparse map queries are part of "
-                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+            raise NotImplementedError("%s does not export %s (sparse map queries and the raycast "
+                                      "are part of libtsdf_hip.so only)" % (self._lib._name, name))
         return fn
 
     def sample(self, points, mode="trilinear", min_weight=0.0):
@@ -286,6 +286,55 @@ class TSDFVolume:
                        g.ctypes.data_as(_abi.FP), v.ctypes.data_as(C.POINTER(C.c_uint8))),
                     "sample_cloud")
         return s, w, g, v.astype(bool)
+
+    def _raycast_args(self, pose, t_min, t_max, step, mode):
+        """(pose pointer or None, its array, t_min, t_max, step, mode code) of a raycast call."""
+        if mode not in _abi.SAMPLE_MODES:
+            raise ValueError("mode must be one of %s" % sorted(_abi.SAMPLE_MODES))
+        T = None
+        if pose is not None:
+            T = np.asarray(pose, np.float64)
+            if T.shape == (4, 4):
+                T = T[:3]
+            if T.shape != (3, 4):
+                raise ValueError("pose must be a (3, 4) or (4, 4) matrix")
+            T = np.ascontiguousarray(T)
+        step = self.voxel_size / 2 if step is None else step
+        return (None if T is None else _d3(T)), T, float(t_min), float(t_max), float(step), \
+            _abi.SAMPLE_MODES[mode]
+
+    def raycast(self, origins, dirs, pose=None, t_min=0.0, t_max=100.0, step=None, mode="nearest",
+                min_weight=0.0, normals=True):
+        """What the map shows along rays: (depth (N,), normal (N, 3) or None, hit (N,) bool).
+        origins: (N, 3), or (3,) for one origin shared by every ray; dirs: (N, 3), not normalised
+        by the call (depth counts in units of |dir|: unit directions give metres).  pose (3x4 or
+        4x4, world from the rays' frame) transforms both; None takes the rays as given.  The ray
+        is sampled every `step` (default voxel_size / 2) from t_min to t_max as `sample` samples
+        points, and hits at the first front-facing zero crossing between two valid samples; depth
+        is 0 and the normal (0, 0, 0) where there is none.  mode "trilinear" needs all eight
+        voxels around a sample observed, which a sparse map seldom offers: "nearest" is the
+        default.  include/tsdf_hip_raycast.h states the arithmetic."""
+        fn = self._sample_fn("tsdf_raycast")
+        pp, keep, t_min, t_max, step, code = self._raycast_args(pose, t_min, t_max, step, mode)
+        d = np.asarray(dirs, np.float32)
+        if d.ndim != 2 or d.shape[1] != 3:
+            raise ValueError("dirs must be np.ndarray(n, 3)")
+        o = np.asarray(origins, np.float32)
+        if o.shape == (3,):
+            o = np.broadcast_to(o, d.shape)
+        if o.shape != d.shape:
+            raise ValueError("origins must be (3,) or match dirs")
+        o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+        n = d.shape[0]
+        depth = np.empty(n, np.float32)
+        normal = np.empty((n, 3), np.float32) if normals else None
+        hit = np.empty(n, np.uint8)
+        self._check(fn(self._ctx, o.ctypes.data_as(_abi.FP), d.ctypes.data_as(_abi.FP), n, pp,
+                       t_min, t_max, step, code, float(min_weight), depth.ctypes.data_as(_abi.FP),
+                       normal.ctypes.data_as(_abi.FP) if normals else None,
+                       hit.ctypes.data_as(_abi.U8P)), "raycast")
+        del keep
+        return depth, normal, hit.astype(bool)
 
     def extract_triangle_mesh(self, fill_holes=True, min_weight=0.0, table="generated",
                               halo=None):
@@ -564,6 +613,21 @@ class HipTSDFVolume(TSDFVolume):
                        float(min_weight), C.c_void_p(int(d_sdf_ptr or 0)),
                        C.c_void_p(int(d_weight_ptr or 0)), C.c_void_p(int(d_grad_ptr or 0)),
                        C.c_void_p(int(d_valid_ptr or 0))), "sample_device")
+
+    def raycast_device(self, d_org_ptr, d_dir_ptr, n, d_depth_ptr, d_normal_ptr, d_hit_ptr,
+                       pose=None, t_min=0.0, t_max=100.0, step=None, mode="nearest",
+                       min_weight=0.0):
+        """`raycast` for n device rays (origins and directions, n x 3 float32 each) into
+        caller-given device buffers: depth (n float32), normal (3 n float32, or None / 0 to skip
+        it), hit (n uint8).  The rays must be complete before the call; the outputs are complete
+        when it returns."""
+        fn = self._sample_fn("tsdf_raycast_device")
+        pp, keep, t_min, t_max, step, code = self._raycast_args(pose, t_min, t_max, step, mode)
+        self._check(fn(self._ctx, C.c_void_p(int(d_org_ptr or 0)), C.c_void_p(int(d_dir_ptr or 0)),
+                       int(n), pp, t_min, t_max, step, code, float(min_weight),
+                       C.c_void_p(int(d_depth_ptr or 0)), C.c_void_p(int(d_normal_ptr or 0)),
+                       C.c_void_p(int(d_hit_ptr or 0))), "raycast_device")
+        del keep
 
     def align_terms(self, points, pose, min_weight=0.0, n=None):
         """Gauss-Newton terms of the point-to-TSDF error of a cloud under `pose` (3x4 or 4x4, world
