@@ -1,5 +1,7 @@
-// pack_pool.h -- the host staging thread pool of libtsdf_hip (tsdf_capi.cpp), plain C++ so the CPU
-// tests can build and stress it without a GPU (tests/test_pack_pool.py).
+// pack_pool.h -- the host staging thread pool of libtsdf_hip, plain C++ so the CPU tests can build
+// and stress it without a GPU (tests/test_pack_pool.py).  tsdf_capi.cpp creates one per context;
+// host_pack.h's run_parts is what drives them (one pool, or several side by side with part
+// offsets), next to the record packer whose work they share.
 #pragma once
 #include <atomic>
 #include <chrono>

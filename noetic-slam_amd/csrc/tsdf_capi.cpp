@@ -30,6 +30,7 @@
 #include "../../include/tsdf_hip_raycast.h"
 #include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
+#include "host_pack.h"
 #include "pack_pool.h"
 #include "tsdf_device.h"
 
@@ -449,14 +450,9 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
     ScanRec* ds = c->d_ring + (size_t)slot * (MAX_BATCH + 1);
     std::memcpy(hs, D.s, (D.n_scans + 1) * sizeof(ScanRec));
     c->ht.lap(9);
-#ifdef TSDF_RING_MEMCPY
-    HIPCHK(c, hipMemcpyAsync(ds, hs, (D.n_scans + 1) * sizeof(ScanRec), hipMemcpyHostToDevice, st));
-#error "TSDF_RING_MEMCPY: the ring progress word is written by k_upload"
-#else
     HIPCHK(c, launch_upload(c->d_ring_src + (size_t)slot * (MAX_BATCH + 1), ds,
                             (uint32_t)((D.n_scans + 1) * sizeof(ScanRec)), c->d_ring_done, seq + 1,
                             st));
-#endif
     c->ht.lap(10);
     c->ht.lap(2);
     const BatchRef B{D.n_scans, D.n_blocks, ds};
@@ -1439,6 +1435,14 @@ static void set_pose(BatchDesc& D, uint32_t s, const ScanPose& P) {
     D.s[s].zz = P.z[2];
 }
 
+// A caller's row-major 3x4 pose as the kernels take it (a null pose: unused, zeros)
+static OsPose os_pose(const double pose[12]) {
+    OsPose P{};
+    if (pose)
+        for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    return P;
+}
+
 // The pending batch's device staging buffer (host and single device scans are queued there).  A
 // new pending batch takes the buffer the last launched host batch did not use; that buffer's
 // previous reader must be complete and, with growth possible, committed: an overflowed batch is
@@ -1507,229 +1511,196 @@ static void idx_share(const tsdf_ctx* c, uint64_t n, uint64_t& lo, uint64_t& hi)
     hi = (uint64_t)((unsigned __int128)n * (k + 1) / N);
 }
 
-static int integrate_impl(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step,
-                          uint32_t xyz_offset, int32_t xyz_is_f64, const ScanPose& P) {
+// ---- host-pointer input: a packer (host_pack.h pack_xyz), a scheduler (run_parts
+// over the contexts' staging pools) and a stager (stage_acquire / stage_commit) ------------------
+
+// The argument rules the host-pointer entry points share
+static RecordView records_of(const void* pts, uint32_t point_step, uint32_t xyz_offset,
+                             int32_t xyz_is_f64) {
+    return RecordView{static_cast<const char*>(pts), point_step, xyz_offset, xyz_is_f64 != 0};
+}
+
+static int check_layout(tsdf_ctx* c, const RecordView& V) {
+    return V.layout_ok() ? TSDF_OK : fail(c, TSDF_EINVAL, "point_step/xyz_offset inconsistent");
+}
+
+// pose = (x, y, z, qx, qy, qz, qw): the quaternion need not be normalised, only finite and nonzero
+static bool quat_ok(const double pose[7]) {
+    const double qn = pose[3] * pose[3] + pose[4] * pose[4] + pose[5] * pose[5] + pose[6] * pose[6];
+    return qn > 0.0 && std::isfinite(qn);
+}
+
+// A free pinned staging buffer (*hb, at *h) for a scan of n points: room in the pending batch
+// (launching it first if needed), then the buffer whose previous copy to the device is complete.
+static int stage_acquire(tsdf_ctx* c, uint64_t n, int* hb, float** h) {
+    HIPCHK(c, hipSetDevice(c->device));
+    const int rc = pend_room(c, n);
+    if (rc) return rc;
+    *hb = c->stage_cur;
+    c->stage_cur ^= 1;
+    HIPCHK(c, hipEventSynchronize(c->stage_done[*hb]));
+    *h = c->h_stage[*hb];
+    return TSDF_OK;
+}
+
+// The n points packed into h (stage_acquire's buffer hb) go to the device and join the pending
+// batch as a scan seen from P, on the current device.
+static int stage_commit(tsdf_ctx* c, int hb, const float* h, uint64_t n, const ScanPose& P) {
+    const int rc = pend_stage_buffer(c);
+    if (rc) return rc;
+    if (n)
+        HIPCHK(c, hipMemcpyAsync(c->stage2[c->pend_stage] + 3 * (uint64_t)c->pend.s[c->pend.n_scans].off,
+                                 h, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->stage_done[hb], c->stream));
+    return pend_push(c, n, P);
+}
+
+static int integrate_impl(tsdf_ctx* c, RecordView V, uint64_t n, const ScanPose& P) {
     if (border_busy(c)) return TSDF_EINVAL;
-    const uint32_t need = xyz_is_f64 ? 24u : 12u;
-    if (point_step < need || xyz_offset > point_step - need)
-        return fail(c, TSDF_EINVAL, "point_step/xyz_offset inconsistent");
+    if (const int rc = check_layout(c, V)) return rc;
     {  // the context's share of the cloud (all of it unless index-sharded)
         uint64_t lo, hi;
         idx_share(c, n, lo, hi);
-        if (pts) pts = static_cast<const char*>(pts) + lo * point_step;
+        if (V.base) V.base += lo * V.point_step;
         n = hi - lo;
     }
     if (n > c->max_points)
         return fail(c, TSDF_EINVAL, "scan of %llu points exceeds max_points %llu",
                     (unsigned long long)n, (unsigned long long)c->max_points);
-    HIPCHK(c, hipSetDevice(c->device));
-    {
-        const int rc = pend_room(c, n);
-        if (rc) return rc;
-    }
-    const int b = c->stage_cur;
-    c->stage_cur ^= 1;
-    HIPCHK(c, hipEventSynchronize(c->stage_done[b]));  // previous copy out of this buffer is done
-    float* h = c->h_stage[b];
-    const char* base = static_cast<const char*>(pts);
-    if (!xyz_is_f64 && point_step == 12 && xyz_offset == 0) {
-        std::memcpy(h, base, n * 12);
-    } else {
-        auto pack = [&](uint64_t i0, uint64_t i1) {
-            for (uint64_t i = i0; i < i1; i++) {
-                const char* q = base + i * point_step + xyz_offset;
-                if (xyz_is_f64) {
-                    double d[3];
-                    std::memcpy(d, q, sizeof d);
-                    h[3 * i] = (float)d[0];
-                    h[3 * i + 1] = (float)d[1];
-                    h[3 * i + 2] = (float)d[2];
-                } else {
-                    std::memcpy(h + 3 * i, q, 12);
-                }
-            }
-        };
-        if (c->pack && n >= (1u << 15)) {
-            const uint64_t parts = (uint64_t)c->pack->parts();
-            c->pack->run([&](int k) { pack(n * k / parts, n * (k + 1) / parts); });
-        } else {
-            pack(0, n);
-        }
-    }
-    int rc = pend_stage_buffer(c);
-    if (rc) return rc;
-    if (n) {
-        HIPCHK(c, hipMemcpyAsync(c->stage2[c->pend_stage] + 3 * (uint64_t)c->pend.s[c->pend.n_scans].off,
-                                 h, n * 12, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipEventRecord(c->stage_done[b], c->stream));
-    return pend_push(c, n, P);
+    int hb;
+    float* h;
+    if (const int rc = stage_acquire(c, n, &hb, &h)) return rc;
+    // on the context's own staging threads; packed fp32 is one memcpy, on the calling thread
+    run_parts(&c->pack, V.packed_f32() ? 0 : 1, n,
+              [&](int, uint64_t i0, uint64_t i1) { pack_xyz(V, i0, i1, h + 3 * i0); });
+    return stage_commit(c, hb, h, n, P);
 }
 
 int tsdf_integrate(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step,
                    uint32_t xyz_offset, int32_t xyz_is_f64, const double origin[3]) {
     if (!c) return TSDF_EINVAL;
     if ((!pts && n) || !origin) return fail(c, TSDF_EINVAL, "null argument");
-    return integrate_impl(c, pts, n, point_step, xyz_offset, xyz_is_f64, pose_of_origin(origin));
+    return integrate_impl(c, records_of(pts, point_step, xyz_offset, xyz_is_f64), n,
+                          pose_of_origin(origin));
+}
+
+int tsdf_integrate_pose(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step,
+                        uint32_t xyz_offset, int32_t xyz_is_f64, const double pose[7]) {
+    if (!c) return TSDF_EINVAL;
+    if ((!pts && n) || !pose) return fail(c, TSDF_EINVAL, "null argument");
+    if (!quat_ok(pose)) return fail(c, TSDF_EINVAL, "pose quaternion is zero");
+    return integrate_impl(c, records_of(pts, point_step, xyz_offset, xyz_is_f64), n, pose_of(pose));
 }
 
 }  // extern "C"
 
+// ---- tsdf_integrate_sectors: one host cloud for N sector-sharded contexts ----------------------
+
+// The error text of a sectors call is read from ctxs[0] (the Python wrapper, the node): a failure
+// of context k > 0 is mirrored there.  Call it on the thread that owns the call.
+static int mirror(tsdf_ctx* const* ctxs, uint32_t k, int rc) {
+    if (rc && k) ctxs[0]->err = ctxs[k]->err;
+    return rc;
+}
+
+// stage_commit of one of a sectors call's contexts: on its device first
+static int stage_commit_on(tsdf_ctx* c, int hb, const float* h, uint64_t n, const ScanPose& P) {
+    HIPCHK(c, hipSetDevice(c->device));
+    return stage_commit(c, hb, h, n, P);
+}
+
+// The contexts' staging pools, for run_parts (a context without threads has none)
+static void pools_of(tsdf_ctx* const* ctxs, uint32_t n, PackPool** pools) {
+    for (uint32_t k = 0; k < n; k++) pools[k] = ctxs[k]->pack;
+}
+
 // tsdf_integrate_sectors without a host split (tsdf_params.sector_input FANOUT / H2D): the cloud
-// is packed ONCE into ctxs[0]'s pinned buffer h[0] (on every context's staging threads), and every
+// is packed ONCE into ctxs[0]'s pinned buffer hx (on every context's staging threads), and every
 // context receives all of it -- its kernels drop the other sectors' rays (R.sec_on), so the fields
 // are those of the split, bit for bit.
 //   FANOUT: one H2D copy into ctxs[0]'s staging (the leader); the other contexts (followers) take
 //           the scan into their pending batch and copy the batch's points from the leader's staging
 //           in ONE device-to-device copy before they launch it (fan_copy: hipMemcpyPeerAsync, xGMI
 //           with peer access, tsdf_create_sharded) -- O(1) API calls per follower per scan.
-//   H2D:    every context copies h[0] over its own PCIe link; ctxs[0]'s stream waits for them all
-//           before it records h[0]'s reuse event.
-static int sectors_broadcast(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, uint64_t n,
-                             uint32_t point_step, uint32_t xyz_offset, int32_t xyz_is_f64,
-                             const ScanPose& P, float* const* h, const int* hb, bool fanout) {
-    tsdf_ctx* c0 = ctxs[0];
-    float* hx = h[0];
-    const char* base = static_cast<const char*>(pts);
-    auto pack = [&](uint64_t i0, uint64_t i1) {
-        if (!xyz_is_f64 && point_step == 12 && xyz_offset == 0) {
-            std::memcpy(hx + 3 * i0, base + 12 * i0, (i1 - i0) * 12);
-            return;
-        }
-        for (uint64_t i = i0; i < i1; i++) {
-            const char* q = base + i * point_step + xyz_offset;
-            if (xyz_is_f64) {
-                double d[3];
-                std::memcpy(d, q, sizeof d);
-                hx[3 * i] = (float)d[0];
-                hx[3 * i + 1] = (float)d[1];
-                hx[3 * i + 2] = (float)d[2];
-            } else {
-                std::memcpy(hx + 3 * i, q, 12);
+//   H2D:    every context copies hx over its own PCIe link; ctxs[0]'s stream waits for them all
+//           before it records hx's reuse event.
+// One follower's leg: the scan's n points, at offset off0 of the leader c0's staging buffer buf0
+// (device) and in hx (host), join c's pending batch.
+static int broadcast_follower(tsdf_ctx* c, tsdf_ctx* c0, float* buf0, uint64_t off0,
+                              const float* hx, uint64_t n, const ScanPose& P, bool fanout) {
+    HIPCHK(c, hipSetDevice(c->device));
+    int rc = pend_stage_buffer(c);
+    if (rc) return rc;
+    const uint64_t off = c->pend.s[c->pend.n_scans].off;
+    if (fanout) {
+        // batch-granular: extend the follower's uncopied range when it continues in the same
+        // leader buffer at the same offset (lockstep batches), else copy what it holds first
+        if (c->fan_src != c0 || c->fan_buf != buf0 || c->fan_hi != off || off != off0) {
+            rc = fan_copy(c);
+            if (rc) return rc;
+            if (c->fan_src && c->fan_src != c0) {  // a new leader
+                auto& v = c->fan_src->fan_followers;
+                v.erase(std::remove(v.begin(), v.end(), c), v.end());
+            }
+            if (std::find(c0->fan_followers.begin(), c0->fan_followers.end(), c) ==
+                c0->fan_followers.end())
+                c0->fan_followers.push_back(c);
+            c->fan_src = c0;
+            c->fan_buf = buf0;
+            c->fan_lo = c->fan_hi = off;
+            if (off != off0) {  // out of lockstep: this scan alone, now
+                c->fan_buf = nullptr;  // nothing pending; the next scan starts afresh
+                if (n) {
+                    rc = fan_copy_range(c, c0, c->stage2[c->pend_stage] + 3 * off, buf0 + 3 * off0,
+                                        n * 12);
+                    if (rc) return rc;
+                }
             }
         }
-    };
-    // every context's staging threads pack a share of the points
-    int pbase[TSDF_MAX_WORLD + 1];
-    pbase[0] = 0;
-    for (uint32_t k = 0; k < n_ctx; k++)
-        pbase[k + 1] = pbase[k] + (ctxs[k]->pack ? ctxs[k]->pack->parts() - (k ? 1 : 0) : (k ? 0 : 1));
-    const int parts = n >= (1u << 15) ? pbase[n_ctx] : 1;
-    auto part = [&](int q) { pack(n * (uint64_t)q / parts, n * (uint64_t)(q + 1) / parts); };
-    if (parts == 1) {
-        part(0);
-    } else {
-        for (uint32_t k = 1; k < n_ctx; k++)
-            if (ctxs[k]->pack) ctxs[k]->pack->start(part, pbase[k] - 1);
-        if (c0->pack) c0->pack->run(part);
-        else part(0);
-        for (uint32_t k = 1; k < n_ctx; k++)
-            if (ctxs[k]->pack) ctxs[k]->pack->wait();
+        if (c->fan_buf) c->fan_hi = off + n;
+    } else if (n) {
+        // H2D: this context's own PCIe copy of hx; the leader must not reuse hx first
+        HIPCHK(c, hipMemcpyAsync(c->stage2[c->pend_stage] + 3 * off, hx, n * 12,
+                                 hipMemcpyHostToDevice, c->stream));
+        if (!c->bc_ev) HIPCHK(c, hipEventCreateWithFlags(&c->bc_ev, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->bc_ev, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c0->stream, c->bc_ev, 0));  // (reported by c: see mirror)
     }
+    return pend_push(c, n, P);  // a full batch launches here (fan-out: after its copy)
+}
+
+static int sectors_broadcast(tsdf_ctx* const* ctxs, uint32_t n_ctx, const RecordView& V,
+                             uint64_t n, const ScanPose& P, float* hx, int hb0, bool fanout) {
+    tsdf_ctx* c0 = ctxs[0];
+    // every context's staging threads pack a share of the points
+    PackPool* pools[TSDF_MAX_WORLD];
+    pools_of(ctxs, n_ctx, pools);
+    run_parts(pools, n_ctx, n,
+              [&](int, uint64_t i0, uint64_t i1) { pack_xyz(V, i0, i1, hx + 3 * i0); });
     c0->split_ht.lap(1);  // TSDF_HOST_TIMING: 0 prep, 1 pack, 2 copies + queue
     // the leader's H2D copy first
     HIPCHK(c0, hipSetDevice(c0->device));
-    int rc = pend_stage_buffer(c0);
-    if (rc) return rc;
+    if (const int rc = pend_stage_buffer(c0)) return rc;
     const uint64_t off0 = c0->pend.s[c0->pend.n_scans].off;
     float* buf0 = c0->stage2[c0->pend_stage];
     if (n) HIPCHK(c0, hipMemcpyAsync(buf0 + 3 * off0, hx, n * 12, hipMemcpyHostToDevice, c0->stream));
     if (!c0->bc_ev) HIPCHK(c0, hipEventCreateWithFlags(&c0->bc_ev, hipEventDisableTiming));
     HIPCHK(c0, hipEventRecord(c0->bc_ev, c0->stream));
-    for (uint32_t k = 1; k < n_ctx; k++) {
-        tsdf_ctx* c = ctxs[k];
-        HIPCHK(c, hipSetDevice(c->device));
-        rc = pend_stage_buffer(c);
-        if (rc) return rc;
-        const uint64_t off = c->pend.s[c->pend.n_scans].off;
-        if (fanout) {
-            // batch-granular: extend the follower's uncopied range when it continues in the same
-            // leader buffer at the same offset (lockstep batches), else copy what it holds first
-            if (c->fan_src != c0 || c->fan_buf != buf0 || c->fan_hi != off || off != off0) {
-                rc = fan_copy(c);
-                if (rc) return rc;
-                if (c->fan_src && c->fan_src != c0) {  // a new leader
-                    auto& v = c->fan_src->fan_followers;
-                    v.erase(std::remove(v.begin(), v.end(), c), v.end());
-                }
-                if (std::find(c0->fan_followers.begin(), c0->fan_followers.end(), c) ==
-                    c0->fan_followers.end())
-                    c0->fan_followers.push_back(c);
-                c->fan_src = c0;
-                c->fan_buf = buf0;
-                c->fan_lo = c->fan_hi = off;
-                if (off != off0) {  // out of lockstep: this scan alone, now
-                    c->fan_buf = nullptr;  // nothing pending; the next scan starts afresh
-                    if (n) {
-                        rc = fan_copy_range(c, c0, c->stage2[c->pend_stage] + 3 * off,
-                                            buf0 + 3 * off0, n * 12);
-                        if (rc) return rc;
-                    }
-                }
-            }
-            if (c->fan_buf) c->fan_hi = off + n;
-        } else if (n) {
-            // H2D: this context's own PCIe copy of h[0]; the leader must not reuse h[0] first
-            HIPCHK(c, hipMemcpyAsync(c->stage2[c->pend_stage] + 3 * off, hx, n * 12,
-                                     hipMemcpyHostToDevice, c->stream));
-            if (!c->bc_ev) HIPCHK(c, hipEventCreateWithFlags(&c->bc_ev, hipEventDisableTiming));
-            HIPCHK(c, hipEventRecord(c->bc_ev, c->stream));
-            HIPCHK(c0, hipStreamWaitEvent(c0->stream, c->bc_ev, 0));
-        }
-        rc = pend_push(c, n, P);  // a full batch launches here (fan-out: after its copy)
-        if (rc) return rc;
-    }
+    for (uint32_t k = 1; k < n_ctx; k++)
+        if (const int rc = mirror(ctxs, k, broadcast_follower(ctxs[k], c0, buf0, off0, hx, n, P, fanout)))
+            return rc;
     HIPCHK(c0, hipSetDevice(c0->device));
-    HIPCHK(c0, hipEventRecord(c0->stage_done[hb[0]], c0->stream));
-    rc = pend_push(c0, n, P);
-    if (rc) return rc;
+    HIPCHK(c0, hipEventRecord(c0->stage_done[hb0], c0->stream));
+    if (const int rc = pend_push(c0, n, P)) return rc;
     c0->split_ht.lap(2);
     return TSDF_OK;
 }
 
-extern "C" {
-
-// One host cloud for N sector-sharded contexts (the live N-GPU input path): every
-// point is classified once (the kernels' in_sector rule on each context's bounds) and packed into
-// its context's pinned staging; each context then copies only its sector's points to its GPU, so a
-// scan crosses PCIe once in total, split over the N links.
-static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, uint64_t n,
-                        uint32_t point_step, uint32_t xyz_offset, int32_t xyz_is_f64,
-                        const ScanPose& P);
-
-int tsdf_integrate_sectors(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, uint64_t n,
-                           uint32_t point_step, uint32_t xyz_offset, int32_t xyz_is_f64,
-                           const double pose[7]) {
-    if (!ctxs || n_ctx == 0 || n_ctx > TSDF_MAX_WORLD) return TSDF_EINVAL;
-    for (uint32_t k = 0; k < n_ctx; k++)
-        if (!ctxs[k]) return TSDF_EINVAL;
-    if (!pose) return fail(ctxs[0], TSDF_EINVAL, "null argument");
-    const double qn = pose[3] * pose[3] + pose[4] * pose[4] + pose[5] * pose[5] + pose[6] * pose[6];
-    if (!(qn > 0.0) || !std::isfinite(qn)) return fail(ctxs[0], TSDF_EINVAL, "pose quaternion is zero");
-    return sectors_impl(ctxs, n_ctx, pts, n, point_step, xyz_offset, xyz_is_f64, pose_of(pose));
-}
-
-// ABI v9 (ADVICE r4): the sectors path with a bare origin keeps tsdf_integrate's "no orientation"
-// (Voxblox's constant weight), so the sharded field equals the unsharded one for every semantics
-int tsdf_integrate_sectors_origin(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts,
-                                  uint64_t n, uint32_t point_step, uint32_t xyz_offset,
-                                  int32_t xyz_is_f64, const double origin[3]) {
-    if (!ctxs || n_ctx == 0 || n_ctx > TSDF_MAX_WORLD) return TSDF_EINVAL;
-    for (uint32_t k = 0; k < n_ctx; k++)
-        if (!ctxs[k]) return TSDF_EINVAL;
-    if (!origin) return fail(ctxs[0], TSDF_EINVAL, "null argument");
-    return sectors_impl(ctxs, n_ctx, pts, n, point_step, xyz_offset, xyz_is_f64,
-                        pose_of_origin(origin));
-}
-
-}  // extern "C"
-
 // tsdf_integrate_sectors under TSDF_SECTOR_RULE_INDEX: context k receives points [lo_k, hi_k)
-// (idx_share).  The packing is one parallel pass on the staging threads of ALL the contexts (each
-// part of the cloud to the pinned buffers of the contexts whose shares it covers), then per
+// (idx_share).  The packing is one parallel pass on the staging threads of the first few contexts
+// (each part of the cloud to the pinned buffers of the contexts whose shares it covers), then per
 // context one H2D copy of its share and the scan joins its pending batch.
-static int sectors_shares(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, uint64_t n,
-                          uint32_t point_step, uint32_t xyz_offset, int32_t xyz_is_f64,
+static int sectors_shares(tsdf_ctx* const* ctxs, uint32_t n_ctx, const RecordView& V, uint64_t n,
                           const ScanPose& P) {
     tsdf_ctx* c0 = ctxs[0];
     HostTiming& ht = c0->split_ht;
@@ -1746,47 +1717,10 @@ static int sectors_shares(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts
     lo[n_ctx] = n;
     float* h[TSDF_MAX_WORLD];
     int hb[TSDF_MAX_WORLD];
-    for (uint32_t k = 0; k < n_ctx; k++) {  // room in every pending batch, a free pinned buffer
-        tsdf_ctx* c = ctxs[k];
-        HIPCHK(c, hipSetDevice(c->device));
-        const int rc = pend_room(c, lo[k + 1] - lo[k]);
-        if (rc) {
-            if (k) c0->err = c->err;
+    for (uint32_t k = 0; k < n_ctx; k++)  // room in every pending batch, a free pinned buffer
+        if (const int rc = mirror(ctxs, k, stage_acquire(ctxs[k], lo[k + 1] - lo[k], &hb[k], &h[k])))
             return rc;
-        }
-        hb[k] = c->stage_cur;
-        c->stage_cur ^= 1;
-        HIPCHK(c, hipEventSynchronize(c->stage_done[hb[k]]));
-        h[k] = c->h_stage[hb[k]];
-    }
     ht.lap(0);
-    const char* base = static_cast<const char*>(pts);
-    auto pack = [&](uint64_t i0, uint64_t i1) {
-        uint32_t k = 0;
-        while (k + 1 < n_ctx && lo[k + 1] <= i0) k++;
-        for (uint64_t i = i0; i < i1;) {
-            const uint64_t e = std::min(i1, lo[k + 1]);  // this context's part of [i0, i1)
-            float* dst = h[k] + 3 * (i - lo[k]);
-            if (!xyz_is_f64 && point_step == 12 && xyz_offset == 0) {
-                std::memcpy(dst, base + 12 * i, (e - i) * 12);
-            } else {
-                for (uint64_t j = i; j < e; j++, dst += 3) {
-                    const char* q = base + j * point_step + xyz_offset;
-                    if (xyz_is_f64) {
-                        double d[3];
-                        std::memcpy(d, q, sizeof d);
-                        dst[0] = (float)d[0];
-                        dst[1] = (float)d[1];
-                        dst[2] = (float)d[2];
-                    } else {
-                        std::memcpy(dst, q, 12);
-                    }
-                }
-            }
-            i = e;
-            k++;
-        }
-    };
     // the staging pools of the first few contexts only: every pool's workers spin ~100 us after a
     // job, so N pools' workers (4 N threads) would crowd the calling thread off a 16-CPU share
     // (TSDF_SECTOR_PACK_POOLS, default 2: 8 threads)
@@ -1794,73 +1728,36 @@ static int sectors_shares(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts
         const char* e = std::getenv("TSDF_SECTOR_PACK_POOLS");
         return e ? (uint32_t)std::max(1, std::atoi(e)) : 2u;
     }();
+    PackPool* pools[TSDF_MAX_WORLD];
     const uint32_t np = std::min(n_ctx, max_pools);
-    int pbase[TSDF_MAX_WORLD + 1];
-    pbase[0] = 0;
-    for (uint32_t k = 0; k < np; k++)
-        pbase[k + 1] = pbase[k] + (ctxs[k]->pack ? ctxs[k]->pack->parts() - (k ? 1 : 0) : (k ? 0 : 1));
-    const int parts = n >= (1u << 15) ? pbase[np] : 1;
-    auto part = [&](int q) { pack(n * (uint64_t)q / parts, n * (uint64_t)(q + 1) / parts); };
-    if (parts == 1) {
-        part(0);
-    } else {
-        for (uint32_t k = 1; k < np; k++)
-            if (ctxs[k]->pack) ctxs[k]->pack->start(part, pbase[k] - 1);
-        if (c0->pack) c0->pack->run(part);
-        else part(0);
-        for (uint32_t k = 1; k < np; k++)
-            if (ctxs[k]->pack) ctxs[k]->pack->wait();
-    }
+    pools_of(ctxs, np, pools);
+    run_parts(pools, np, n,
+              [&](int, uint64_t i0, uint64_t i1) { pack_shares(V, i0, i1, lo, n_ctx, h); });
     ht.lap(1);
-    for (uint32_t k = 0; k < n_ctx; k++) {
-        tsdf_ctx* c = ctxs[k];
-        const uint64_t nk = lo[k + 1] - lo[k];
-        HIPCHK(c, hipSetDevice(c->device));
-        int rc = pend_stage_buffer(c);
-        if (!rc && nk)
-            HIPCHK(c, hipMemcpyAsync(c->stage2[c->pend_stage] + 3 * (uint64_t)c->pend.s[c->pend.n_scans].off,
-                                     h[k], nk * 12, hipMemcpyHostToDevice, c->stream));
-        if (!rc) HIPCHK(c, hipEventRecord(c->stage_done[hb[k]], c->stream));
-        if (!rc) rc = pend_push(c, nk, P);
-        if (rc) {
-            if (k) c0->err = c->err;
+    for (uint32_t k = 0; k < n_ctx; k++)
+        if (const int rc = mirror(ctxs, k, stage_commit_on(ctxs[k], hb[k], h[k], lo[k + 1] - lo[k], P)))
             return rc;
-        }
-    }
     HIPCHK(c0, hipSetDevice(c0->device));
     ht.lap(3);
     ht.n++;
     return TSDF_OK;
 }
 
-static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, uint64_t n,
-                        uint32_t point_step, uint32_t xyz_offset, int32_t xyz_is_f64,
+// The sectors call proper, by the contexts' sector_rule and sector_input.  The host split (world
+// rule): every point is classified once (the kernels' in_sector rule on each
+// context's bounds) and packed into its context's pinned staging; each context then copies only
+// its sector's points to its GPU, so a scan crosses PCIe once in total, split over the N links.
+static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const RecordView& V, uint64_t n,
                         const ScanPose& P) {
     tsdf_ctx* c0 = ctxs[0];
-    if (!pts && n) return fail(c0, TSDF_EINVAL, "null argument");
-    const uint32_t need = xyz_is_f64 ? 24u : 12u;
-    if (point_step < need || xyz_offset > point_step - need)
-        return fail(c0, TSDF_EINVAL, "point_step/xyz_offset inconsistent");
+    if (!V.base && n) return fail(c0, TSDF_EINVAL, "null argument");
+    if (const int rc = check_layout(c0, V)) return rc;
     for (uint32_t k = 0; k < n_ctx; k++)
-        if (border_busy(ctxs[k])) {
-            if (k) c0->err = ctxs[k]->err;
-            return TSDF_EINVAL;
-        }
-    for (uint32_t k = 0; k < n_ctx; k++) {
-        const tsdf_ctx* c = ctxs[k];
-        const bool sharded = n_ctx == 1 ? c->p.n_sectors <= 1 : c->p.n_sectors == n_ctx;
-        if (!sharded || (n_ctx > 1 && (c->p.sector != k || c->p.sector_yaw0 != c0->p.sector_yaw0 ||
-                                       c->p.sector_rule != c0->p.sector_rule)))
-            return fail(c0, TSDF_EINVAL,
-                        "context %u is not sector %u of %u (same sector_yaw0 and sector_rule)", k, k,
-                        n_ctx);
-    }
+        if (border_busy(ctxs[k])) return mirror(ctxs, k, TSDF_EINVAL);
     // TSDF_SECTOR_RULE_INDEX (ABI v10): context k's share is a contiguous index range of the
-    // cloud: every context's staging threads pack the whole cloud once, each point into its own
-    // context's pinned buffer, then each context copies only its share over its own PCIe link --
-    // one pass over the cloud, no classification, no fan-out (a Merged context bundles its share)
-    if (n_ctx > 1 && c0->idx_rule) return sectors_shares(ctxs, n_ctx, pts, n, point_step,
-                                                         xyz_offset, xyz_is_f64, P);
+    // cloud, whatever sector_input says: one pass over the cloud, no classification, no fan-out
+    // (a Merged context bundles its share)
+    if (n_ctx > 1 && c0->idx_rule) return sectors_shares(ctxs, n_ctx, V, n, P);
     for (uint32_t k = 0; k < n_ctx; k++) {
         const tsdf_ctx* c = ctxs[k];
         if (n > c->max_points)  // a context may receive every point
@@ -1873,40 +1770,28 @@ static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, 
     // room in every pending batch, and each context's free pinned buffer
     float* h[TSDF_MAX_WORLD];
     int hb[TSDF_MAX_WORLD];
-    for (uint32_t k = 0; k < n_ctx; k++) {
-        tsdf_ctx* c = ctxs[k];
-        HIPCHK(c, hipSetDevice(c->device));
-        const int rc = pend_room(c, n);
-        if (rc) return rc;
-        hb[k] = c->stage_cur;
-        c->stage_cur ^= 1;
-        HIPCHK(c, hipEventSynchronize(c->stage_done[hb[k]]));
-        h[k] = c->h_stage[hb[k]];
-    }
+    for (uint32_t k = 0; k < n_ctx; k++)
+        if (const int rc = mirror(ctxs, k, stage_acquire(ctxs[k], n, &hb[k], &h[k]))) return rc;
     int mode = n_ctx > 1 ? c0->p.sector_input : TSDF_SECTOR_INPUT_SPLIT;
     // MergedTsdfIntegrator bundles the whole scan's points before the sector filter: a host split
     // would bundle each sector's points apart
     if (mode == TSDF_SECTOR_INPUT_SPLIT && n_ctx > 1 && c0->merged) mode = TSDF_SECTOR_INPUT_FANOUT;
     if (mode == TSDF_SECTOR_INPUT_FANOUT || mode == TSDF_SECTOR_INPUT_H2D) {
         ht.lap(0);
-        const int rc = sectors_broadcast(ctxs, n_ctx, pts, n, point_step, xyz_offset, xyz_is_f64,
-                                         P, h, hb, mode == TSDF_SECTOR_INPUT_FANOUT);
-        if (rc) return rc;
+        if (const int rc = sectors_broadcast(ctxs, n_ctx, V, n, P, h[0], hb[0],
+                                             mode == TSDF_SECTOR_INPUT_FANOUT))
+            return rc;
         ht.lap(3);
         ht.n++;
         return TSDF_OK;
     }
     // Two passes over point chunks, on the staging threads of ALL the contexts (each GPU's host
-    // share): (1) read the records once, pack xyz into c0's scratch and classify each point,
-    // counting per (part, sector); (2) copy the packed points, still in cache, to their sector's
-    // pinned buffer at the part's prefix (the parts keep the input order within a sector).
-    const char* base = static_cast<const char*>(pts);
-    // The sector of a point: the starts s_k of the N sectors, rotated to ascending order
-    // u_j = s_(r+j), give sector (r + #{j: a >= u_j} - 1) mod N -- the kernels' in_sector test on
-    // every context's [lo, hi) bounds (the wrap sector holds a < u_0 and a >= u_(N-1)), one
-    // pseudo-angle and N compares per point.  NaN: no sector (every kernel drops the ray).
+    // share): (1) read the records once, pack xyz into c0's scratch and classify each point
+    // (host_pack.h sector_of_angle: one pseudo-angle and N compares), counting per (part, sector);
+    // (2) copy the packed points, still in cache, to their sector's pinned buffer at the part's
+    // prefix (the parts keep the input order within a sector).
     const bool sharded = n_ctx > 1 && c0->R.sec_on;
-    float u[TSDF_MAX_WORLD];
+    float u[TSDF_MAX_WORLD];  // the sector starts, ascending from context r0's
     uint32_t r0 = 0;
     if (sharded) {
         for (uint32_t k = 1; k < n_ctx; k++)
@@ -1917,21 +1802,9 @@ static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, 
                 return fail(c0, TSDF_EINVAL, "sector starts of the contexts are not distinct");
         }
     }
-    // parts: c0's pool (caller + workers), then every other context's workers
-    int pbase[TSDF_MAX_WORLD + 1];
-    pbase[0] = 0;
-    for (uint32_t k = 0; k < n_ctx; k++)
-        pbase[k + 1] = pbase[k] + (ctxs[k]->pack ? ctxs[k]->pack->parts() - (k ? 1 : 0) : (k ? 0 : 1));
-    const int parts = n >= (1u << 15) ? pbase[n_ctx] : 1;
-    auto run_parts = [&](const std::function<void(int)>& f) {
-        if (parts == 1) return f(0);
-        for (uint32_t k = 1; k < n_ctx; k++)
-            if (ctxs[k]->pack) ctxs[k]->pack->start(f, pbase[k] - 1);
-        if (c0->pack) c0->pack->run(f);
-        else f(0);
-        for (uint32_t k = 1; k < n_ctx; k++)
-            if (ctxs[k]->pack) ctxs[k]->pack->wait();
-    };
+    PackPool* pools[TSDF_MAX_WORLD];
+    pools_of(ctxs, n_ctx, pools);
+    const int parts = part_count(pools, n_ctx, n);
     if (c0->split_xyz.size() < 3 * n) {
         c0->split_xyz.resize(3 * n);
         c0->split_sec.resize(n);
@@ -1939,38 +1812,19 @@ static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, 
     float* xyz = c0->split_xyz.data();
     int8_t* sec = c0->split_sec.data();
     std::vector<uint64_t> cnt((size_t)parts * n_ctx, 0), at((size_t)parts * n_ctx, 0);
-    auto classify = [&](int part) {
-        const uint64_t i0 = n * part / parts, i1 = n * (part + 1) / parts;
+    auto classify = [&](int part, uint64_t i0, uint64_t i1) {
+        pack_xyz(V, i0, i1, xyz + 3 * i0);
         uint64_t cl[TSDF_MAX_WORLD] = {};  // local counts (the parts' rows share cache lines)
         for (uint64_t i = i0; i < i1; i++) {
-            const char* q = base + i * point_step + xyz_offset;
-            float* v = xyz + 3 * i;
-            if (xyz_is_f64) {
-                double d[3];
-                std::memcpy(d, q, sizeof d);
-                v[0] = (float)d[0];
-                v[1] = (float)d[1];
-                v[2] = (float)d[2];
-            } else {
-                std::memcpy(v, q, 12);
-            }
-            int k = 0;
-            if (sharded) {
-                const float a = pseudo_angle(v[0] - ox, v[1] - oy);
-                uint32_t c = 0;
-                for (uint32_t j = 0; j < n_ctx; j++) c += a >= u[j] ? 1u : 0u;
-                uint32_t m = r0 + c + n_ctx - 1u;  // (r0 + c - 1) mod N without a division: m < 3N
-                m -= m >= n_ctx ? n_ctx : 0u;
-                m -= m >= n_ctx ? n_ctx : 0u;
-                k = a != a ? -1 : (int)m;
-            }
+            const float* v = xyz + 3 * i;
+            const int k = sharded ? sector_of_angle(pseudo_angle(v[0] - ox, v[1] - oy), u, r0, n_ctx)
+                                  : 0;
             sec[i] = (int8_t)k;
             if (k >= 0) cl[k]++;
         }
         for (uint32_t k = 0; k < n_ctx; k++) cnt[(size_t)part * n_ctx + k] = cl[k];
     };
-    auto scatter = [&](int part) {
-        const uint64_t i0 = n * part / parts, i1 = n * (part + 1) / parts;
+    auto scatter = [&](int part, uint64_t i0, uint64_t i1) {
         float* dst[TSDF_MAX_WORLD];
         for (uint32_t k = 0; k < n_ctx; k++) dst[k] = h[k] + 3 * at[(size_t)part * n_ctx + k];
         for (uint64_t i = i0; i < i1; i++) {
@@ -1981,7 +1835,7 @@ static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, 
         }
     };
     ht.lap(0);
-    run_parts(classify);
+    run_parts(pools, n_ctx, n, classify);
     ht.lap(1);
     std::vector<uint64_t> tot(n_ctx, 0);
     for (uint32_t k = 0; k < n_ctx; k++)
@@ -1989,23 +1843,13 @@ static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, 
             at[(size_t)q * n_ctx + k] = tot[k];
             tot[k] += cnt[(size_t)q * n_ctx + k];
         }
-    run_parts(scatter);
+    run_parts(pools, n_ctx, n, scatter);
     ht.lap(2);
     // each context: its sector's points to its GPU, into its pending batch -- the contexts are
     // independent, so the staging threads issue them side by side (the copy and launch API calls
     // cost ~10 us each on the host)
     int crc[TSDF_MAX_WORLD] = {};
-    auto push_ctx = [&](uint32_t k) -> int {
-        tsdf_ctx* c = ctxs[k];
-        HIPCHK(c, hipSetDevice(c->device));
-        int rc = pend_stage_buffer(c);
-        if (rc) return rc;
-        if (tot[k])
-            HIPCHK(c, hipMemcpyAsync(c->stage2[c->pend_stage] + 3 * (uint64_t)c->pend.s[c->pend.n_scans].off,
-                                     h[k], tot[k] * 12, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipEventRecord(c->stage_done[hb[k]], c->stream));
-        return pend_push(c, tot[k], P);
-    };
+    auto push_ctx = [&](uint32_t k) { return stage_commit_on(ctxs[k], hb[k], h[k], tot[k], P); };
     const int cparts = c0->pack && n_ctx > 1 ? std::min<int>(c0->pack->parts(), (int)n_ctx) : 1;
     if (cparts > 1) {
         c0->pack->run([&](int part) {
@@ -2016,21 +1860,54 @@ static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, 
         for (uint32_t k = 0; k < n_ctx; k++) crc[k] = push_ctx(k);
     }
     for (uint32_t k = 0; k < n_ctx; k++)
-        if (crc[k]) return crc[k];
+        if (crc[k]) return mirror(ctxs, k, crc[k]);
     ht.lap(3);
     ht.n++;
     return TSDF_OK;
 }
 
+// The ctxs / n_ctx rule of the sectors entry points: n_ctx contexts, context k sector k of n_ctx
+// with the same sector_yaw0 and sector_rule (one context: not sharded)
+static int check_sector_ctxs(tsdf_ctx* const* ctxs, uint32_t n_ctx) {
+    if (!ctxs || n_ctx == 0 || n_ctx > TSDF_MAX_WORLD) return TSDF_EINVAL;
+    for (uint32_t k = 0; k < n_ctx; k++)
+        if (!ctxs[k]) return TSDF_EINVAL;
+    const tsdf_ctx* c0 = ctxs[0];
+    for (uint32_t k = 0; k < n_ctx; k++) {
+        const tsdf_ctx* c = ctxs[k];
+        const bool sharded = n_ctx == 1 ? c->p.n_sectors <= 1 : c->p.n_sectors == n_ctx;
+        if (!sharded || (n_ctx > 1 && (c->p.sector != k || c->p.sector_yaw0 != c0->p.sector_yaw0 ||
+                                       c->p.sector_rule != c0->p.sector_rule)))
+            return fail(ctxs[0], TSDF_EINVAL,
+                        "context %u is not sector %u of %u (same sector_yaw0 and sector_rule)", k, k,
+                        n_ctx);
+    }
+    return TSDF_OK;
+}
+
 extern "C" {
 
-int tsdf_integrate_pose(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step,
-                        uint32_t xyz_offset, int32_t xyz_is_f64, const double pose[7]) {
-    if (!c) return TSDF_EINVAL;
-    if ((!pts && n) || !pose) return fail(c, TSDF_EINVAL, "null argument");
-    const double qn = pose[3] * pose[3] + pose[4] * pose[4] + pose[5] * pose[5] + pose[6] * pose[6];
-    if (!(qn > 0.0) || !std::isfinite(qn)) return fail(c, TSDF_EINVAL, "pose quaternion is zero");
-    return integrate_impl(c, pts, n, point_step, xyz_offset, xyz_is_f64, pose_of(pose));
+int tsdf_integrate_sectors(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts, uint64_t n,
+                           uint32_t point_step, uint32_t xyz_offset, int32_t xyz_is_f64,
+                           const double pose[7]) {
+    const int rc = check_sector_ctxs(ctxs, n_ctx);
+    if (rc) return rc;
+    if (!pose) return fail(ctxs[0], TSDF_EINVAL, "null argument");
+    if (!quat_ok(pose)) return fail(ctxs[0], TSDF_EINVAL, "pose quaternion is zero");
+    return sectors_impl(ctxs, n_ctx, records_of(pts, point_step, xyz_offset, xyz_is_f64), n,
+                        pose_of(pose));
+}
+
+// ABI v9 (ADVICE r4): the sectors path with a bare origin keeps tsdf_integrate's "no orientation"
+// (Voxblox's constant weight), so the sharded field equals the unsharded one for every semantics
+int tsdf_integrate_sectors_origin(tsdf_ctx* const* ctxs, uint32_t n_ctx, const void* pts,
+                                  uint64_t n, uint32_t point_step, uint32_t xyz_offset,
+                                  int32_t xyz_is_f64, const double origin[3]) {
+    const int rc = check_sector_ctxs(ctxs, n_ctx);
+    if (rc) return rc;
+    if (!origin) return fail(ctxs[0], TSDF_EINVAL, "null argument");
+    return sectors_impl(ctxs, n_ctx, records_of(pts, point_step, xyz_offset, xyz_is_f64), n,
+                        pose_of_origin(origin));
 }
 
 // origins: 3 doubles per scan (pose_stride 3) or poses: 7 per scan (pose_stride 7)
@@ -2085,12 +1962,9 @@ int tsdf_integrate_batch_device(tsdf_ctx* c, const float* d_xyz, const uint64_t*
 int tsdf_integrate_batch_device_pose(tsdf_ctx* c, const float* d_xyz, const uint64_t* offs,
                                      uint32_t n_scans, const double* poses) {
     if (c && poses)
-        for (uint32_t s = 0; s < n_scans; s++) {
-            const double* q = poses + 7 * (uint64_t)s;
-            const double qn = q[3] * q[3] + q[4] * q[4] + q[5] * q[5] + q[6] * q[6];
-            if (!(qn > 0.0) || !std::isfinite(qn))
+        for (uint32_t s = 0; s < n_scans; s++)
+            if (!quat_ok(poses + 7 * (uint64_t)s))
                 return fail(c, TSDF_EINVAL, "pose %u: quaternion is zero", s);
-        }
     return batch_device_impl(c, d_xyz, offs, n_scans, poses, 7);
 }
 
@@ -2122,8 +1996,8 @@ int tsdf_integrate_device(tsdf_ctx* c, const float* d_xyz, uint64_t n, const dou
     return pend_push(c, n, pose_of_origin(origin));
 }
 
-int tsdf_sync(tsdf_ctx* c) {
-    if (!c) return TSDF_EINVAL;
+// flush + drain, ignoring (but keeping) the overflow flag for read-out calls
+static int drain(tsdf_ctx* c) {
     HIPCHK(c, hipSetDevice(c->device));
     int rc = settle(c);
     if (rc) return rc;
@@ -2131,7 +2005,12 @@ int tsdf_sync(tsdf_ctx* c) {
     rc = check_and_replay(c);
     if (rc) return rc;
     if (c->timer) c->timer->harvest();
-    rc = emit_metrics(c);
+    return emit_metrics(c);
+}
+
+int tsdf_sync(tsdf_ctx* c) {
+    if (!c) return TSDF_EINVAL;
+    const int rc = drain(c);
     if (rc) return rc;
     uint32_t ovf = 0;
     HIPCHK(c, hipMemcpy(&ovf, &c->G->overflow, sizeof ovf, hipMemcpyDeviceToHost));
@@ -2149,18 +2028,6 @@ int tsdf_sync(tsdf_ctx* c) {
                     (ovf & OVF_SPN) ? "span list full; " : "");
     }
     return TSDF_OK;
-}
-
-// flush + drain, ignoring (but keeping) the overflow flag for read-out calls
-static int drain(tsdf_ctx* c) {
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = settle(c);
-    if (rc) return rc;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    rc = check_and_replay(c);
-    if (rc) return rc;
-    if (c->timer) c->timer->harvest();
-    return emit_metrics(c);
 }
 
 int tsdf_query_dense(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], float* sdf,
@@ -2232,9 +2099,9 @@ int tsdf_sample(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step, u
     if (!c) return TSDF_EINVAL;
     int rc = sample_args(c, mode, min_weight);
     if (rc) return rc;
-    const uint32_t need = xyz_is_f64 ? 24u : 12u;
-    if (point_step < need || xyz_offset > point_step - need)
-        return fail(c, TSDF_EINVAL, "point_step/xyz_offset inconsistent");
+    const RecordView V = records_of(pts, point_step, xyz_offset, xyz_is_f64);
+    rc = check_layout(c, V);
+    if (rc) return rc;
     if (n && (!pts || !sdf || !weight || !valid)) return fail(c, TSDF_EINVAL, "sample: null buffer");
     if (!n) return TSDF_OK;
     rc = drain(c);
@@ -2246,22 +2113,10 @@ int tsdf_sample(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step, u
     float *dx = d, *ds = d + 3 * piece, *dw = d + 4 * piece, *dg = d + 5 * piece;
     uint8_t* dv = reinterpret_cast<uint8_t*>(d + 8 * piece);
     std::vector<float> h(3 * piece);
-    const char* base = static_cast<const char*>(pts);
     hipError_t e = hipSuccess;
     for (uint64_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
         const uint64_t m = std::min(piece, n - i0);
-        for (uint64_t i = 0; i < m; i++) {
-            const char* q = base + (i0 + i) * point_step + xyz_offset;
-            if (xyz_is_f64) {
-                double v[3];
-                std::memcpy(v, q, sizeof v);
-                h[3 * i] = (float)v[0];
-                h[3 * i + 1] = (float)v[1];
-                h[3 * i + 2] = (float)v[2];
-            } else {
-                std::memcpy(&h[3 * i], q, 12);
-            }
-        }
+        pack_xyz(V, i0, i0 + m, h.data());
         e = hipMemcpyAsync(dx, h.data(), m * 12, hipMemcpyHostToDevice, c->stream);
         if (e == hipSuccess)
             e = launch_sample(c->T, c->Pl, c->R, dx, m, mode, min_weight, ds, dw, grad ? dg : nullptr,
@@ -2289,8 +2144,7 @@ int tsdf_align_terms_device(tsdf_ctx* c, const float* d_xyz, uint64_t n, const d
     if (rc) return rc;
     constexpr size_t words = ((size_t)ALIGN_MAX_WG + 1) * ALIGN_PART;
     if (!c->align_part) HIPCHK(c, hipMalloc(&c->align_part, words * sizeof(double)));
-    OsPose P;
-    for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    const OsPose P = os_pose(pose);
     HIPCHK(c, launch_align(c->T, c->Pl, c->R, d_xyz, n, P, min_weight, c->align_part, c->stream));
     double r[29];  // H's upper triangle row-major, b, sum r^2, the valid count
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2356,9 +2210,7 @@ int tsdf_raycast_device(tsdf_ctx* c, const float* d_org, const float* d_dir, uin
     if (!n) return TSDF_OK;
     rc = drain(c);
     if (rc) return rc;
-    OsPose P;
-    if (pose)
-        for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    const OsPose P = os_pose(pose);
     HIPCHK(c, launch_raycast(c->T, c->Pl, c->R, d_org, d_dir, n, pose ? &P : nullptr, t_min, step,
                              raycast_samples(t_min, t_max, step), mode, min_weight, d_depth,
                              d_normal, d_hit, c->stream));
@@ -2376,9 +2228,7 @@ int tsdf_raycast(tsdf_ctx* c, const float* org, const float* dir, uint64_t n, co
     if (!n) return TSDF_OK;
     rc = drain(c);
     if (rc) return rc;
-    OsPose P;
-    if (pose)
-        for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    const OsPose P = os_pose(pose);
     const uint32_t n_k = raycast_samples(t_min, t_max, step);
     // pieces of at most max_points: (origin, direction) up, (depth, normal, hit) down
     const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(c->max_points, 1));
@@ -2540,8 +2390,7 @@ int tsdf_os_cartesian_device(tsdf_ctx* c, const uint32_t* d_range, uint64_t n, c
     if (n && (!d_range || !d_dir || !d_off || !d_xyz)) return fail(c, TSDF_EINVAL, "null argument");
     if (!pose) return fail(c, TSDF_EINVAL, "null pose");
     HIPCHK(c, hipSetDevice(c->device));
-    OsPose P;
-    for (int k = 0; k < 12; k++) P.m[k] = (float)pose[k];
+    const OsPose P = os_pose(pose);
     HIPCHK(c, launch_os_xyz(d_range, n, d_dir, d_off, P, d_xyz, c->stream));
     return TSDF_OK;
 }

@@ -364,6 +364,64 @@ def test_integrate_sectors_bitwise(sim, n, f64, mode, rule):
         assert all(v.stats()["n_points_in"] == total for v in g)  # every context got the cloud
 
 
+def _records(pts, f64):
+    """(n, 3) points as PointCloud2-style records with xyz inside: fp32 in 32 B at offset 4, or
+    fp64 in 40 B at offset 8 (float-valued doubles: the library rounds fp64 input to fp32, the
+    oracle's fp64 walk reads it as given); the other bytes are filler."""
+    n = pts.shape[0]
+    if f64:
+        step, off, xyz = 40, 8, pts.astype(np.float64)
+    else:
+        step, off, xyz = 32, 4, pts.astype(np.float32)
+    rec = np.full((n, step), 0xA5, np.uint8)
+    rec[:, off:off + 3 * xyz.itemsize] = np.ascontiguousarray(xyz).view(np.uint8).reshape(n, -1)
+    return rec.tobytes(), step, off, xyz
+
+
+@pytest.mark.parametrize("f64", [False, True])
+@pytest.mark.parametrize("mode,rule", [("split", "world"), ("fanout", "world"), ("h2d", "world"),
+                                       ("fanout", "index")])
+def test_integrate_sectors_records_bitwise(sim, mode, rule, f64):
+    """The four transfers of tsdf_integrate_sectors fed with strided records (not packed arrays)
+    through integrate_sectors_cloud: two scans above the 2^15-point threshold of the multi-part
+    packing schedule and one of 1000 points (a single part), three contexts on one GPU.  Every
+    context equals its oracle twin bit for bit, with test_integrate_sectors_bitwise's accounting
+    of the points each context received."""
+    from tsdf_map import integrate_sectors_cloud
+    n, yaw0 = 3, 0.4
+    g = [hip(n_sectors=n, sector=r, sector_yaw0=yaw0, max_batch=2, sector_input=mode,
+             sector_rule=rule) for r in range(n)]
+    o = [ora(n_sectors=n, sector=r, sector_yaw0=yaw0, sector_rule=rule) for r in range(n)]
+    rays = total = 0
+    for k, small in ((0, False), (9, True), (1, False)):
+        pts, org = sim.scan(k)
+        pts = pts[np.linspace(0, pts.shape[0] - 1, 1000).astype(np.int64)] if small else pts[::3]
+        assert small or pts.shape[0] >= 1 << 15
+        # rays along every sector start (boundary ties) and NaN rows (no sector: dropped)
+        th = yaw0 + 2 * np.pi * np.arange(n) / n
+        edge = org[None, :] + np.stack([7.0 * np.cos(th), 7.0 * np.sin(th), np.zeros(n)], 1)
+        pts = np.concatenate([pts, edge.astype(np.float32),
+                              np.full((3, 3), np.nan, np.float32)]).astype(np.float32)
+        data, step, off, xyz = _records(pts, f64)
+        q = np.array([0.0, 0.0, np.sin(0.1 * k), np.cos(0.1 * k)])
+        integrate_sectors_cloud(g, data, pts.shape[0], step, off, np.concatenate([org, q]),
+                                xyz_is_f64=f64)
+        for v in o:
+            v.integrate(xyz, org)
+        rays += pts.shape[0] - 3
+        total += pts.shape[0]
+    for r in range(n):
+        g[r].sync()
+        assert voxels_equal_bitwise(g[r].export_voxels(), o[r].export_voxels()), r
+    if rule == "index":  # each context received exactly its share
+        assert sum(v.stats()["n_points_in"] for v in g) == total
+        assert max(v.stats()["n_points_in"] for v in g) <= -(-total // n) + 3
+    elif mode == "split":
+        assert sum(v.stats()["n_points_in"] for v in g) == rays  # each point went to one context
+    else:
+        assert all(v.stats()["n_points_in"] == total for v in g)  # every context got the cloud
+
+
 def test_fanout_out_of_lockstep(sim):
     """The fan-out copies a follower's pending points from the leader's staging once per batch;
     partial flushes (a read-out of the leader alone), a follower's own scan in between, and the
