@@ -30,6 +30,7 @@
 #include "../../include/tsdf_hip_raycast.h"
 #include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
+#include "brick_key.h"
 #include "host_pack.h"
 #include "pack_pool.h"
 #include "tsdf_device.h"
@@ -39,6 +40,7 @@ using namespace tsdf;
 static_assert(TSDF_MAX_BATCH == MAX_BATCH, "header and device batch limits differ");
 static_assert(TSDF_TILE_WORDS == TILE_WORDS && TSDF_MAX_WORLD == MAX_WORLD, "border tile layout differs");
 static_assert(TSDF_MC_TABLES == MC_TABLES, "marching-cubes table count differs");
+static_assert(BRICK_KEY_BIAS == BRICK_COORD_BIAS, "host and device brick keys differ");
 
 namespace {
 
@@ -752,25 +754,49 @@ static int grow_capacity(tsdf_ctx* c, uint64_t need) {
     return TSDF_OK;
 }
 
-// Double the fallback-pair lists (OVF_FB) of both batch parities, up to the 26-bit index space.
-static int grow_fb(tsdf_ctx* c) {
-    const uint64_t nf = std::min<uint64_t>(2ull * c->Wk.max_fb, 1ull << 26);
-    if (nf <= c->Wk.max_fb) return fail(c, TSDF_ENOMEM, "fallback pair list at its limit");
-    uint4* f[2] = {nullptr, nullptr};
-    hipError_t e = hipMalloc(&f[0], nf * sizeof(uint4));
-    if (e == hipSuccess) e = hipMalloc(&f[1], nf * sizeof(uint4));
+// Double one of the work lists in both batch parities, up to `limit` entries of `bytes` each.
+// `counted`: the growth shows in tsdf_get_stats' n_grows (the fallback pairs' never has).
+template <class T>
+static int grow_list(tsdf_ctx* c, T* Work::*list, uint32_t Work::*max, uint64_t limit, size_t bytes,
+                     const char* what, bool counted) {
+    const uint64_t n = std::min<uint64_t>(2ull * (c->Wk.*max), limit);
+    if (n <= c->Wk.*max) return fail(c, TSDF_ENOMEM, "%s at its limit", what);
+    T* f[2] = {nullptr, nullptr};
+    hipError_t e = hipMalloc(&f[0], n * bytes);
+    if (e == hipSuccess) e = hipMalloc(&f[1], n * bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
         for (auto q : f) if (q) (void)hipFree(q);
-        return fail(c, TSDF_ENOMEM, "fallback pair list allocation failed");
+        return fail(c, TSDF_ENOMEM, "%s allocation failed", what);
     }
     for (int q = 0; q < 2; q++) {
-        (void)hipFree(c->W2[q].fb);
-        c->W2[q].fb = f[q];
-        c->W2[q].max_fb = (uint32_t)nf;
+        (void)hipFree(c->W2[q].*list);
+        c->W2[q].*list = f[q];
+        c->W2[q].*max = (uint32_t)n;
     }
-    c->Wk.max_fb = (uint32_t)nf;
+    c->Wk.*max = (uint32_t)n;
+    if (counted) c->n_grows++;
     return TSDF_OK;
+}
+
+// The fallback-pair lists (OVF_FB), up to the 26-bit index space.
+static int grow_fb(tsdf_ctx* c) {
+    return grow_list(c, &Work::fb, &Work::max_fb, 1ull << 26, sizeof(uint4), "fallback pair list",
+                     false);
+}
+
+// The sample lists (OVF_SMP), up to the 32-bit sample index (single walk: the workgroup regions,
+// up to the span record's 30-bit sample position).
+static uint64_t smp_limit(const tsdf_ctx* c) { return c->fused ? (1ull << 30) : 0xFFFFFFF0ull; }
+static int grow_smp(tsdf_ctx* c) {
+    return grow_list(c, &Work::smp, &Work::max_smp, smp_limit(c), smp_bytes(c->R.sem), "sample list",
+                     true);
+}
+
+// The span lists (OVF_SPN, single walk).
+static int grow_spn(tsdf_ctx* c) {
+    return grow_list(c, &Work::spn, &Work::max_spn, 0xFFFFFFF0ull, sizeof(uint32_t), "span list",
+                     true);
 }
 
 // Every launched batch complete: the context stream waits for them and drains.
@@ -785,52 +811,6 @@ static int drain_all(tsdf_ctx* c) {
 // batches from it (their inputs are still valid), until a round succeeds.  Without growth (hard
 // limit, or a non-growable overflow) the batches are re-run committing what fits, and tsdf_sync
 // reports the overflow.
-// Double both parities' sample lists (OVF_SMP), up to the 32-bit sample index (single walk: the
-// workgroup regions, up to the span record's 30-bit sample position).
-static uint64_t smp_limit(const tsdf_ctx* c) { return c->fused ? (1ull << 30) : 0xFFFFFFF0ull; }
-static int grow_smp(tsdf_ctx* c) {
-    const uint64_t ns = std::min<uint64_t>(2ull * c->Wk.max_smp, smp_limit(c));
-    if (ns <= c->Wk.max_smp) return fail(c, TSDF_ENOMEM, "sample list at its limit");
-    uint2* f[2] = {nullptr, nullptr};
-    hipError_t e = hipMalloc(&f[0], ns * smp_bytes(c->R.sem));
-    if (e == hipSuccess) e = hipMalloc(&f[1], ns * smp_bytes(c->R.sem));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (auto q : f) if (q) (void)hipFree(q);
-        return fail(c, TSDF_ENOMEM, "sample list allocation failed");
-    }
-    for (int q = 0; q < 2; q++) {
-        (void)hipFree(c->W2[q].smp);
-        c->W2[q].smp = f[q];
-        c->W2[q].max_smp = (uint32_t)ns;
-    }
-    c->Wk.max_smp = (uint32_t)ns;
-    c->n_grows++;
-    return TSDF_OK;
-}
-
-// Double both parities' span lists (OVF_SPN, single walk).
-static int grow_spn(tsdf_ctx* c) {
-    const uint64_t ns = std::min<uint64_t>(2ull * c->Wk.max_spn, 0xFFFFFFF0ull);
-    if (ns <= c->Wk.max_spn) return fail(c, TSDF_ENOMEM, "span list at its limit");
-    uint32_t* f[2] = {nullptr, nullptr};
-    hipError_t e = hipMalloc(&f[0], ns * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&f[1], ns * sizeof(uint32_t));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        for (auto q : f) if (q) (void)hipFree(q);
-        return fail(c, TSDF_ENOMEM, "span list allocation failed");
-    }
-    for (int q = 0; q < 2; q++) {
-        (void)hipFree(c->W2[q].spn);
-        c->W2[q].spn = f[q];
-        c->W2[q].max_spn = (uint32_t)ns;
-    }
-    c->Wk.max_spn = (uint32_t)ns;
-    c->n_grows++;
-    return TSDF_OK;
-}
-
 static int check_and_replay(tsdf_ctx* c) {
     for (int round = 0; round < 64; round++) {
         struct { uint32_t pool_count, overflow, failed, retry, fail_id; } g;
@@ -1596,10 +1576,25 @@ int tsdf_integrate_pose(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point
 
 // ---- tsdf_integrate_sectors: one host cloud for N sector-sharded contexts ----------------------
 
-// The error text of a sectors call is read from ctxs[0] (the Python wrapper, the node): a failure
-// of context k > 0 is mirrored there.  Call it on the thread that owns the call.
+// The ctxs / n rule every multi-context entry point starts with
+static bool ctxs_ok(tsdf_ctx* const* ctxs, uint32_t n) {
+    if (!ctxs || n == 0 || n > TSDF_MAX_WORLD) return false;
+    for (uint32_t k = 0; k < n; k++)
+        if (!ctxs[k]) return false;
+    return true;
+}
+
+// The error text of a multi-context call is read from ctxs[0] (the Python wrapper, the node).
+// mirror: the caller knows that context k failed, and its text replaces ctxs[0]'s.  Call it on the
+// thread that owns the call.  first_error (border reduce, sharded mesh: the failing context is not
+// tracked through their steps) copies the first other context's text, and only when ctxs[0] holds
+// none at all, so a text left in ctxs[0] by an earlier call wins there.
 static int mirror(tsdf_ctx* const* ctxs, uint32_t k, int rc) {
     if (rc && k) ctxs[0]->err = ctxs[k]->err;
+    return rc;
+}
+static int first_error(tsdf_ctx* const* ctxs, uint32_t n, int rc) {
+    for (uint32_t k = 1; k < n && ctxs[0]->err.empty(); k++) ctxs[0]->err = ctxs[k]->err;
     return rc;
 }
 
@@ -1869,9 +1864,7 @@ static int sectors_impl(tsdf_ctx* const* ctxs, uint32_t n_ctx, const RecordView&
 // The ctxs / n_ctx rule of the sectors entry points: n_ctx contexts, context k sector k of n_ctx
 // with the same sector_yaw0 and sector_rule (one context: not sharded)
 static int check_sector_ctxs(tsdf_ctx* const* ctxs, uint32_t n_ctx) {
-    if (!ctxs || n_ctx == 0 || n_ctx > TSDF_MAX_WORLD) return TSDF_EINVAL;
-    for (uint32_t k = 0; k < n_ctx; k++)
-        if (!ctxs[k]) return TSDF_EINVAL;
+    if (!ctxs_ok(ctxs, n_ctx)) return TSDF_EINVAL;
     const tsdf_ctx* c0 = ctxs[0];
     for (uint32_t k = 0; k < n_ctx; k++) {
         const tsdf_ctx* c = ctxs[k];
@@ -2030,6 +2023,67 @@ int tsdf_sync(tsdf_ctx* c) {
     return TSDF_OK;
 }
 
+}  // extern "C"
+
+// ---- read-out and exchange: what the calls below share -------------------------------------------
+
+// A call's temporary device memory: allocated on a context's device, freed there at scope end,
+// whichever way the call returns.  take() hands a buffer over to a longer-lived owner (the border
+// transaction's brd_sent and brd_backup, freed by tsdf_border_commit_device).
+struct Scratch {
+    std::vector<std::pair<int, void*>> held;  // (device, buffer)
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    // n elements on c's device (at least 16 bytes, so never a null pointer)
+    template <class T>
+    hipError_t get(tsdf_ctx* c, T** p, size_t n) {
+        void* q = nullptr;
+        hipError_t e = hipSetDevice(c->device);
+        if (e == hipSuccess) e = hipMalloc(&q, std::max<size_t>(n * sizeof(T), 16));
+        if (e == hipSuccess) held.push_back({c->device, q});
+        *p = e == hipSuccess ? static_cast<T*>(q) : nullptr;
+        return e;
+    }
+    // the same as a status code, the text in c (for the calls that go on to roll back)
+    template <class T>
+    int get_or_fail(tsdf_ctx* c, T** p, size_t n) {
+        HIPCHK(c, get(c, p, n));
+        return TSDF_OK;
+    }
+    template <class T>
+    T* take(T* p) {
+        held.erase(std::find_if(held.begin(), held.end(), [p](const auto& q) { return q.second == p; }));
+        return p;
+    }
+    ~Scratch() {
+        for (auto& q : held) {
+            (void)hipSetDevice(q.first);
+            (void)hipFree(q.second);
+        }
+    }
+};
+
+// The caller's current device, restored at scope end: the multi-context calls switch devices.
+struct DeviceGuard {
+    int dev = -1;
+    DeviceGuard() { if (hipGetDevice(&dev) != hipSuccess) dev = -1; }
+    DeviceGuard(const DeviceGuard&) = delete;
+    DeviceGuard& operator=(const DeviceGuard&) = delete;
+    ~DeviceGuard() { if (dev >= 0) (void)hipSetDevice(dev); }
+};
+
+// Bytes from context src's device buffer to context dst's: an xGMI peer copy, or a device copy
+// when both share a GPU.
+static hipError_t copy_between(tsdf_ctx* dst, void* d_dst, tsdf_ctx* src, const void* d_src,
+                               size_t bytes) {
+    if (!bytes) return hipSuccess;
+    return src->device == dst->device ? hipMemcpy(d_dst, d_src, bytes, hipMemcpyDeviceToDevice)
+                                      : hipMemcpyPeer(d_dst, dst->device, d_src, src->device, bytes);
+}
+
+extern "C" {
+
 int tsdf_query_dense(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], float* sdf,
                      float* weight) {
     if (!c) return TSDF_EINVAL;
@@ -2049,32 +2103,37 @@ int tsdf_query_dense(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], floa
     int rc = drain(c);
     if (rc) return rc;
     if (!total) return TSDF_OK;
+    Scratch tmp;
     float *ds = nullptr, *dw = nullptr;
-    HIPCHK(c, hipMalloc(&ds, total * sizeof(float)));
-    hipError_t e = hipMalloc(&dw, total * sizeof(float));
-    if (e == hipSuccess) e = launch_query_dense(c->T, c->Pl, lo, dims, c->R.bg, ds,
-                                                dw, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && sdf) e = hipMemcpy(sdf, ds, total * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && weight) e = hipMemcpy(weight, dw, total * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(ds);
-    if (dw) (void)hipFree(dw);
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "query_dense: %s", hipGetErrorString(e));
+    HIPCHK(c, tmp.get(c, &ds, total));
+    HIPCHK(c, tmp.get(c, &dw, total));
+    HIPCHK(c, launch_query_dense(c->T, c->Pl, lo, dims, c->R.bg, ds, dw, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (sdf) HIPCHK(c, hipMemcpy(sdf, ds, total * 4, hipMemcpyDeviceToHost));
+    if (weight) HIPCHK(c, hipMemcpy(weight, dw, total * 4, hipMemcpyDeviceToHost));
     return TSDF_OK;
 }
 
 // ---- sparse map queries (include/tsdf_hip_sample.h) ---------------------------------------------
 
-// the argument rules the sampling entry points share
-static int sample_args(tsdf_ctx* c, int32_t mode, float min_weight) {
+// The argument rules the sampling and raycast entry points share, in the order they are reported:
+// mode, min_weight, then the caller's own refusal (`own`, a text or null: raycast's lattice rules),
+// then the context's state.
+static int map_query_args(tsdf_ctx* c, const char* what, const char* doing, int32_t mode,
+                          float min_weight, const char* own) {
     if (mode != TSDF_SAMPLE_NEAREST && mode != TSDF_SAMPLE_TRILINEAR)
-        return fail(c, TSDF_EINVAL, "sample: mode must be TSDF_SAMPLE_NEAREST or _TRILINEAR");
-    if (!(min_weight >= 0.0f)) return fail(c, TSDF_EINVAL, "sample: min_weight is negative or NaN");
+        return fail(c, TSDF_EINVAL, "%s: mode must be TSDF_SAMPLE_NEAREST or _TRILINEAR", what);
+    if (!(min_weight >= 0.0f)) return fail(c, TSDF_EINVAL, "%s: min_weight is negative or NaN", what);
+    if (own) return fail(c, TSDF_EINVAL, "%s: %s", what, own);
     if (c->p.n_sectors > 1)
-        return fail(c, TSDF_EINVAL, "sample: the context holds one sector shard of the map "
-                                    "(n_sectors > 1); sampling a sharded field is not supported");
+        return fail(c, TSDF_EINVAL, "%s: the context holds one sector shard of the map "
+                                    "(n_sectors > 1); %s a sharded field is not supported", what, doing);
     if (border_busy(c)) return TSDF_EINVAL;
     return TSDF_OK;
+}
+
+static int sample_args(tsdf_ctx* c, int32_t mode, float min_weight) {
+    return map_query_args(c, "sample", "sampling", mode, min_weight, nullptr);
 }
 
 int tsdf_sample_device(tsdf_ctx* c, const float* d_xyz, uint64_t n, int32_t mode, float min_weight,
@@ -2108,27 +2167,24 @@ int tsdf_sample(tsdf_ctx* c, const void* pts, uint64_t n, uint32_t point_step, u
     if (rc) return rc;
     // pieces of at most max_points: packed fp32 points up, (sdf, weight, grad, valid) down
     const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(c->max_points, 1));
+    Scratch tmp;
     float* d = nullptr;  // xyz (3), sdf, weight, grad (3) per point, then the valid bytes
-    HIPCHK(c, hipMalloc(&d, piece * (8 * sizeof(float) + 1)));
+    HIPCHK(c, tmp.get(c, &d, 8 * piece + (piece + 3) / 4));
     float *dx = d, *ds = d + 3 * piece, *dw = d + 4 * piece, *dg = d + 5 * piece;
     uint8_t* dv = reinterpret_cast<uint8_t*>(d + 8 * piece);
     std::vector<float> h(3 * piece);
-    hipError_t e = hipSuccess;
-    for (uint64_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
+    for (uint64_t i0 = 0; i0 < n; i0 += piece) {
         const uint64_t m = std::min(piece, n - i0);
         pack_xyz(V, i0, i0 + m, h.data());
-        e = hipMemcpyAsync(dx, h.data(), m * 12, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess)
-            e = launch_sample(c->T, c->Pl, c->R, dx, m, mode, min_weight, ds, dw, grad ? dg : nullptr,
-                              dv, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(sdf + i0, ds, m * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(weight + i0, dw, m * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && grad) e = hipMemcpy(grad + 3 * i0, dg, m * 12, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(valid + i0, dv, m, hipMemcpyDeviceToHost);
+        HIPCHK(c, hipMemcpyAsync(dx, h.data(), m * 12, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_sample(c->T, c->Pl, c->R, dx, m, mode, min_weight, ds, dw,
+                                grad ? dg : nullptr, dv, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(sdf + i0, ds, m * 4, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(weight + i0, dw, m * 4, hipMemcpyDeviceToHost));
+        if (grad) HIPCHK(c, hipMemcpy(grad + 3 * i0, dg, m * 12, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(valid + i0, dv, m, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "sample: %s", hipGetErrorString(e));
     return TSDF_OK;
 }
 
@@ -2182,21 +2238,14 @@ static uint32_t raycast_samples(float t_min, float t_max, float step) {
 // the argument rules both raycast entry points share (the buffers apart)
 static int raycast_args(tsdf_ctx* c, float t_min, float t_max, float step, int32_t mode,
                         float min_weight) {
-    if (mode != TSDF_SAMPLE_NEAREST && mode != TSDF_SAMPLE_TRILINEAR)
-        return fail(c, TSDF_EINVAL, "raycast: mode must be TSDF_SAMPLE_NEAREST or _TRILINEAR");
-    if (!(min_weight >= 0.0f)) return fail(c, TSDF_EINVAL, "raycast: min_weight is negative or NaN");
+    const char* own = nullptr;  // the lattice rules, the first that fails
     if (!std::isfinite(t_min) || !std::isfinite(t_max) || !std::isfinite(step))
-        return fail(c, TSDF_EINVAL, "raycast: t_min, t_max and step must be finite");
-    if (!(step > 0.0f)) return fail(c, TSDF_EINVAL, "raycast: step must be positive");
-    if (t_min < 0.0f || t_max < t_min)
-        return fail(c, TSDF_EINVAL, "raycast: need 0 <= t_min <= t_max");
-    if (((double)t_max - (double)t_min) / (double)step >= (double)RAYCAST_MAX_SAMPLES)
-        return fail(c, TSDF_EINVAL, "raycast: (t_max - t_min) / step must stay below 2^20 samples");
-    if (c->p.n_sectors > 1)
-        return fail(c, TSDF_EINVAL, "raycast: the context holds one sector shard of the map "
-                                    "(n_sectors > 1); raycasting a sharded field is not supported");
-    if (border_busy(c)) return TSDF_EINVAL;
-    return TSDF_OK;
+        own = "t_min, t_max and step must be finite";
+    else if (!(step > 0.0f)) own = "step must be positive";
+    else if (t_min < 0.0f || t_max < t_min) own = "need 0 <= t_min <= t_max";
+    else if (((double)t_max - (double)t_min) / (double)step >= (double)RAYCAST_MAX_SAMPLES)
+        own = "(t_max - t_min) / step must stay below 2^20 samples";
+    return map_query_args(c, "raycast", "raycasting", mode, min_weight, own);
 }
 
 int tsdf_raycast_device(tsdf_ctx* c, const float* d_org, const float* d_dir, uint64_t n,
@@ -2232,27 +2281,22 @@ int tsdf_raycast(tsdf_ctx* c, const float* org, const float* dir, uint64_t n, co
     const uint32_t n_k = raycast_samples(t_min, t_max, step);
     // pieces of at most max_points: (origin, direction) up, (depth, normal, hit) down
     const uint64_t piece = std::min<uint64_t>(n, std::max<uint64_t>(c->max_points, 1));
+    Scratch tmp;
     float* d = nullptr;  // org (3), dir (3), depth, normal (3) per ray, then the hit bytes
-    HIPCHK(c, hipMalloc(&d, piece * (10 * sizeof(float) + 1)));
+    HIPCHK(c, tmp.get(c, &d, 10 * piece + (piece + 3) / 4));
     float *dorg = d, *ddir = d + 3 * piece, *dd = d + 6 * piece, *dn = d + 7 * piece;
     uint8_t* dh = reinterpret_cast<uint8_t*>(d + 10 * piece);
-    hipError_t e = hipSuccess;
-    for (uint64_t i0 = 0; i0 < n && e == hipSuccess; i0 += piece) {
+    for (uint64_t i0 = 0; i0 < n; i0 += piece) {
         const uint64_t m = std::min(piece, n - i0);
-        e = hipMemcpyAsync(dorg, org + 3 * i0, m * 12, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(ddir, dir + 3 * i0, m * 12, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess)
-            e = launch_raycast(c->T, c->Pl, c->R, dorg, ddir, m, pose ? &P : nullptr, t_min, step,
-                               n_k, mode, min_weight, dd, normal ? dn : nullptr, dh, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = hipMemcpy(depth + i0, dd, m * 4, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && normal)
-            e = hipMemcpy(normal + 3 * i0, dn, m * 12, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(hit + i0, dh, m, hipMemcpyDeviceToHost);
+        HIPCHK(c, hipMemcpyAsync(dorg, org + 3 * i0, m * 12, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(ddir, dir + 3 * i0, m * 12, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, launch_raycast(c->T, c->Pl, c->R, dorg, ddir, m, pose ? &P : nullptr, t_min, step,
+                                 n_k, mode, min_weight, dd, normal ? dn : nullptr, dh, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(depth + i0, dd, m * 4, hipMemcpyDeviceToHost));
+        if (normal) HIPCHK(c, hipMemcpy(normal + 3 * i0, dn, m * 12, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(hit + i0, dh, m, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "raycast: %s", hipGetErrorString(e));
     return TSDF_OK;
 }
 
@@ -2290,20 +2334,14 @@ int tsdf_export_bricks(tsdf_ctx* c, int32_t* coords, float* sdf, float* weight, 
         w.resize(nb * BRICK_VOX);
         HIPCHK(c, hipMemcpy(w.data(), c->Pl.weight, nb * BRICK_VOX * 4, hipMemcpyDeviceToHost));
     }
-    auto coord = [&](uint64_t k, int a) {
-        return (int32_t)((keys[k] >> (21 * a)) & 0x1FFFFF) - BRICK_COORD_BIAS;
-    };
     std::vector<uint64_t> order(nb);
     std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) {
-        for (int ax = 2; ax >= 0; ax--)
-            if (coord(a, ax) != coord(b, ax)) return coord(a, ax) < coord(b, ax);
-        return false;
-    });
+    std::sort(order.begin(), order.end(),
+              [&](uint64_t a, uint64_t b) { return brick_key_less_zyx(keys[a], keys[b]); });
     for (uint64_t i = 0; i < nb; i++) {
         const uint64_t k = order[i];
         if (coords)
-            for (int a = 0; a < 3; a++) coords[3 * i + a] = coord(k, a);
+            for (int a = 0; a < 3; a++) coords[3 * i + a] = brick_key_coord(keys[k], a);
         if (sdf) std::memcpy(sdf + i * BRICK_VOX, s.data() + k * BRICK_VOX, BRICK_VOX * 4);
         if (weight) std::memcpy(weight + i * BRICK_VOX, w.data() + k * BRICK_VOX, BRICK_VOX * 4);
     }
@@ -2398,53 +2436,32 @@ int tsdf_os_cartesian_device(tsdf_ctx* c, const uint32_t* d_range, uint64_t n, c
 }  // extern "C"
 
 // A context's halo for meshing (ABI v9): received tiles as a small hash table + pool on the
-// context's device (the mesh kernels look neighbours up there first).
+// context's device (the mesh kernels look neighbours up there first), in the caller's scratch.
 struct Halo {
     Table H{};
     Pool HP{};
-    void* mem[4] = {};
-    void release() {
-        for (void*& q : mem)
-            if (q) {
-                (void)hipFree(q);
-                q = nullptr;
-            }
-    }
 };
 
-static int halo_build(tsdf_ctx* c, const uint32_t* d_halo, uint64_t n_halo, Halo& h) {
+static int halo_build(tsdf_ctx* c, const uint32_t* d_halo, uint64_t n_halo, Scratch& tmp, Halo& h) {
     if (!n_halo) return TSDF_OK;
     if (!d_halo) return fail(c, TSDF_EINVAL, "null halo tiles");
     if (n_halo >= (1ull << 30)) return fail(c, TSDF_EINVAL, "too many halo tiles");
     const uint64_t cap = next_pow2(2 * n_halo);
-    hipError_t e = hipMalloc(&h.mem[0], cap * 8);
-    if (e == hipSuccess) e = hipMalloc(&h.mem[1], cap * 4);
-    if (e == hipSuccess) e = hipMalloc(&h.mem[2], n_halo * BRICK_VOX * 8);
-    if (e == hipSuccess) e = hipMalloc(&h.mem[3], 16);
-    if (e == hipSuccess) {
-        h.H.keys = static_cast<uint64_t*>(h.mem[0]);
-        h.H.slots = static_cast<uint32_t*>(h.mem[1]);
-        h.H.mask = cap - 1;
-        h.H.max_bricks = (uint32_t)n_halo;
-        h.HP.sdf = static_cast<float*>(h.mem[2]);
-        h.HP.weight = h.HP.sdf + n_halo * BRICK_VOX;
-        e = launch_fill_u64(h.H.keys, EMPTY_KEY, cap, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(h.mem[3], 0, 16, c->stream);
-    if (e == hipSuccess)
-        e = launch_halo_build(h.H, h.HP, d_halo, (uint32_t)n_halo, static_cast<uint32_t*>(h.mem[3]),
-                              c->stream);
+    uint32_t* d_ovf = nullptr;
+    HIPCHK(c, tmp.get(c, &h.H.keys, cap));
+    HIPCHK(c, tmp.get(c, &h.H.slots, cap));
+    HIPCHK(c, tmp.get(c, &h.HP.sdf, 2 * n_halo * BRICK_VOX));
+    HIPCHK(c, tmp.get(c, &d_ovf, 4));
+    h.H.mask = cap - 1;
+    h.H.max_bricks = (uint32_t)n_halo;
+    h.HP.weight = h.HP.sdf + n_halo * BRICK_VOX;
+    HIPCHK(c, launch_fill_u64(h.H.keys, EMPTY_KEY, cap, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_ovf, 0, 16, c->stream));
+    HIPCHK(c, launch_halo_build(h.H, h.HP, d_halo, (uint32_t)n_halo, d_ovf, c->stream));
     uint32_t ovf = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&ovf, h.mem[3], 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        h.release();
-        return fail(c, TSDF_EHIP, "halo: %s", hipGetErrorString(e));
-    }
-    if (ovf) {
-        h.release();
-        return fail(c, TSDF_EINVAL, "halo: table overflow");
-    }
+    HIPCHK(c, hipMemcpyAsync(&ovf, d_ovf, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (ovf) return fail(c, TSDF_EINVAL, "halo: table overflow");
     return TSDF_OK;
 }
 
@@ -2462,58 +2479,42 @@ static int mesh_impl(tsdf_ctx* c, float min_weight, int32_t table, const uint32_
     if (!nb) return TSDF_OK;
     if (nb >= 0xFFFFFFFFull) return fail(c, TSDF_EINVAL, "too many bricks");
     HIPCHK(c, hipSetDevice(c->device));
+    Scratch tmp;
     Halo halo;
-    rc = halo_build(c, d_halo, n_halo, halo);
+    rc = halo_build(c, d_halo, n_halo, tmp, halo);
     if (rc) return rc;
     // bricks in (z, y, x) order: the triangle soup's order (and the oracle's)
     std::vector<uint64_t> keys(nb);
-    hipError_t e = hipMemcpy(keys.data(), c->T.brick_keys, nb * 8, hipMemcpyDeviceToHost);
-    std::sort(keys.begin(), keys.end(), [](uint64_t a, uint64_t b) {
-        for (int ax = 2; ax >= 0; ax--) {
-            const uint64_t x = (a >> (21 * ax)) & 0x1FFFFF, y = (b >> (21 * ax)) & 0x1FFFFF;
-            if (x != y) return x < y;
-        }
-        return false;
-    });
-    uint64_t* dk = nullptr;
+    HIPCHK(c, hipMemcpy(keys.data(), c->T.brick_keys, nb * 8, hipMemcpyDeviceToHost));
+    std::sort(keys.begin(), keys.end(), brick_key_less_zyx);
+    uint64_t *dk = nullptr, *doff = nullptr;
     uint32_t* dc = nullptr;
-    uint64_t* doff = nullptr;
     float* dt = nullptr;
     std::vector<uint32_t> cnt(nb);
     std::vector<uint64_t> off(nb);
+    HIPCHK(c, tmp.get(c, &dk, nb));
+    HIPCHK(c, tmp.get(c, &dc, nb));
+    HIPCHK(c, hipMemcpyAsync(dk, keys.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_mesh_count(c->T, c->Pl, halo.H, halo.HP, dk, (uint32_t)nb, min_weight, table, dc,
+                                c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), dc, nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     uint64_t total = 0;
-    if (e == hipSuccess) e = hipMalloc(&dk, nb * 8);
-    if (e == hipSuccess) e = hipMalloc(&dc, nb * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(dk, keys.data(), nb * 8, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = launch_mesh_count(c->T, c->Pl, halo.H, halo.HP, dk, (uint32_t)nb, min_weight, table, dc,
-                              c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), dc, nb * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) {
-        for (uint64_t i = 0; i < nb; i++) {
-            off[i] = total;
-            total += cnt[i];
-        }
-        *n_tri = total;
+    for (uint64_t i = 0; i < nb; i++) {
+        off[i] = total;
+        total += cnt[i];
     }
-    if (e == hipSuccess && tri && total <= cap && total) {
-        e = hipMalloc(&doff, nb * 8);
-        if (e == hipSuccess) e = hipMalloc(&dt, total * 36);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(doff, off.data(), nb * 8, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess)
-            e = launch_mesh_emit(c->T, c->Pl, halo.H, halo.HP, dk, (uint32_t)nb, min_weight, table,
-                                 c->R.vs, doff, dt, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(tri, dt, total * 36, hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    for (void* p : {(void*)dk, (void*)dc, (void*)doff, (void*)dt})
-        if (p) (void)hipFree(p);
-    halo.release();
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "extract_mesh: %s", hipGetErrorString(e));
+    *n_tri = total;
     if (tri && total > cap)
         return fail(c, TSDF_EOVERFLOW, "mesh has %llu triangles", (unsigned long long)total);
+    if (!tri || !total) return TSDF_OK;
+    HIPCHK(c, tmp.get(c, &doff, nb));
+    HIPCHK(c, tmp.get(c, &dt, total * 9));
+    HIPCHK(c, hipMemcpyAsync(doff, off.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_mesh_emit(c->T, c->Pl, halo.H, halo.HP, dk, (uint32_t)nb, min_weight, table,
+                               c->R.vs, doff, dt, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tri, dt, total * 36, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return TSDF_OK;
 }
 
@@ -2550,12 +2551,10 @@ int tsdf_import_bricks(tsdf_ctx* c, const int32_t* coords, const float* sdf, con
     {  // bricks must be unique and inside the packable range
         std::vector<uint64_t> k(n);
         for (uint64_t i = 0; i < n; i++) {
-            for (int a = 0; a < 3; a++)
-                if (coords[3 * i + a] < -BRICK_COORD_BIAS || coords[3 * i + a] >= BRICK_COORD_BIAS)
-                    return fail(c, TSDF_EINVAL, "brick coordinate out of range");
-            k[i] = (uint64_t)(coords[3 * i] + BRICK_COORD_BIAS) |
-                   ((uint64_t)(coords[3 * i + 1] + BRICK_COORD_BIAS) << 21) |
-                   ((uint64_t)(coords[3 * i + 2] + BRICK_COORD_BIAS) << 42);
+            const int32_t* b = coords + 3 * i;
+            if (!brick_coord_ok(b[0]) || !brick_coord_ok(b[1]) || !brick_coord_ok(b[2]))
+                return fail(c, TSDF_EINVAL, "brick coordinate out of range");
+            k[i] = brick_key_pack(b[0], b[1], b[2]);
         }
         std::sort(k.begin(), k.end());
         if (std::adjacent_find(k.begin(), k.end()) != k.end())
@@ -2571,26 +2570,19 @@ int tsdf_import_bricks(tsdf_ctx* c, const int32_t* coords, const float* sdf, con
             if (rc == TSDF_EHIP) return rc;
         }
     }
+    Scratch tmp;
     int32_t* dc = nullptr;
     float *ds = nullptr, *dw = nullptr;
     uint32_t* dt = nullptr;
-    hipError_t e = hipMalloc(&dc, n * 12);
-    if (e == hipSuccess) e = hipMalloc(&ds, n * BRICK_VOX * 4);
-    if (e == hipSuccess) e = hipMalloc(&dw, n * BRICK_VOX * 4);
-    if (e == hipSuccess) e = hipMalloc(&dt, n * 4);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, coords, n * 12, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(ds, sdf, n * BRICK_VOX * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(dw, weight, n * BRICK_VOX * 4, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_import(c->T, c->Pl, dc, (uint32_t)n, ds, dw, dt, c->G, merge_cap(c),
-                                           c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dc);
-    (void)hipFree(ds);
-    (void)hipFree(dw);
-    (void)hipFree(dt);
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "import: %s", hipGetErrorString(e));
+    HIPCHK(c, tmp.get(c, &dc, n * 3));
+    HIPCHK(c, tmp.get(c, &ds, n * BRICK_VOX));
+    HIPCHK(c, tmp.get(c, &dw, n * BRICK_VOX));
+    HIPCHK(c, tmp.get(c, &dt, n));
+    HIPCHK(c, hipMemcpyAsync(dc, coords, n * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(ds, sdf, n * BRICK_VOX * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dw, weight, n * BRICK_VOX * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_import(c->T, c->Pl, dc, (uint32_t)n, ds, dw, dt, c->G, merge_cap(c), c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return tsdf_sync(c);
 }
 
@@ -2731,15 +2723,11 @@ int tsdf_brick_keys_device(tsdf_ctx* c, uint64_t* d_keys, uint64_t cap, uint64_t
 
 }  // extern "C"
 
-// tsdf_border_pack_device with the reset optional: keep_rows (not null) receives the device list
-// of the packed bricks' pool slots (caller frees it; null when nothing was packed) and their count,
-// so the caller can reset them later (launch_border_reset)
+// tsdf_border_pack_device's work.  The pool slots of the bricks it packed join the context's
+// border transaction (brd_sent), for the commit's reset.
 static int border_pack_impl(tsdf_ctx* c, const uint64_t* d_all_keys, const uint64_t* counts,
                             uint64_t stride, uint32_t world, uint32_t rank, uint32_t* d_send,
-                            uint64_t cap_rows, uint64_t* send_counts, bool reset,
-                            uint32_t** keep_rows, uint64_t* kept) {
-    if (keep_rows) *keep_rows = nullptr;
-    if (kept) *kept = 0;
+                            uint64_t cap_rows, uint64_t* send_counts) {
     if (!counts || !send_counts || world == 0 || world > TSDF_MAX_WORLD || rank >= world)
         return fail(c, TSDF_EINVAL, "bad world/rank or null counts");
     WorldCounts wc{};
@@ -2756,47 +2744,32 @@ static int border_pack_impl(tsdf_ctx* c, const uint64_t* d_all_keys, const uint6
     for (uint32_t r = 0; r < rank; r++) lower |= wc.n[r] > 0;
     if (!lower) return TSDF_OK;
     if (!d_all_keys) return fail(c, TSDF_EINVAL, "null key buffer");
+    Scratch tmp;
     uint32_t *d_owner = nullptr, *d_aux = nullptr, *d_rows = nullptr;
     uint32_t dest[MAX_WORLD] = {}, cursor[MAX_WORLD] = {};
+    HIPCHK(c, tmp.get(c, &d_owner, nb));
+    HIPCHK(c, tmp.get(c, &d_aux, 2 * MAX_WORLD));
+    HIPCHK(c, launch_border_owner(c->T, (uint32_t)nb, d_all_keys, wc, stride, rank, d_owner, d_aux,
+                                  c->stream));
+    HIPCHK(c, hipMemcpyAsync(dest, d_aux, sizeof dest, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     uint64_t rows = 0;
-    hipError_t e = hipMalloc(&d_owner, nb * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_aux, 2 * MAX_WORLD * 4);
-    if (e == hipSuccess)
-        e = launch_border_owner(c->T, (uint32_t)nb, d_all_keys, wc, stride, rank, d_owner, d_aux,
-                                c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dest, d_aux, sizeof dest, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) {
-        for (uint32_t r = 0; r < world; r++) {
-            cursor[r] = (uint32_t)rows;
-            send_counts[r] = dest[r];
-            rows += dest[r];
-        }
+    for (uint32_t r = 0; r < world; r++) {
+        cursor[r] = (uint32_t)rows;
+        send_counts[r] = dest[r];
+        rows += dest[r];
     }
-    if (e == hipSuccess && d_send && rows) {
-        if (rows > cap_rows) {
-            (void)hipFree(d_owner);
-            (void)hipFree(d_aux);
-            return fail(c, TSDF_EOVERFLOW, "border pack needs %llu rows", (unsigned long long)rows);
-        }
-        e = hipMalloc(&d_rows, rows * 4);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(d_aux + MAX_WORLD, cursor, sizeof cursor, hipMemcpyHostToDevice,
-                               c->stream);
-        if (e == hipSuccess)
-            e = launch_border_pack(c->T, c->Pl, c->R.bg, (uint32_t)nb, rank, d_owner,
-                                   d_aux + MAX_WORLD, d_rows, (uint32_t)rows, d_send, reset,
-                                   c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    if (e == hipSuccess && keep_rows && d_rows) {  // handed to the caller
-        *keep_rows = d_rows;
-        *kept = rows;
-        d_rows = nullptr;
-    }
-    for (void* q : {(void*)d_owner, (void*)d_aux, (void*)d_rows})
-        if (q) (void)hipFree(q);
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "border pack: %s", hipGetErrorString(e));
+    if (!d_send || !rows) return TSDF_OK;
+    if (rows > cap_rows)
+        return fail(c, TSDF_EOVERFLOW, "border pack needs %llu rows", (unsigned long long)rows);
+    HIPCHK(c, tmp.get(c, &d_rows, rows));
+    HIPCHK(c, hipMemcpyAsync(d_aux + MAX_WORLD, cursor, sizeof cursor, hipMemcpyHostToDevice,
+                             c->stream));
+    HIPCHK(c, launch_border_pack(c->T, c->Pl, c->R.bg, (uint32_t)nb, rank, d_owner, d_aux + MAX_WORLD,
+                                 d_rows, (uint32_t)rows, d_send, /*reset=*/false, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->brd_sent = tmp.take(d_rows);
+    c->brd_n_sent = rows;
     return TSDF_OK;
 }
 
@@ -2819,16 +2792,10 @@ int tsdf_border_pack_device(tsdf_ctx* c, const uint64_t* d_all_keys, const uint6
     if (c->brd_n_sent)
         return fail(c, TSDF_EINVAL, "border pack: the open reduce has packed already (commit first)");
     HIPCHK(c, hipSetDevice(c->device));
-    uint32_t* rows = nullptr;
-    uint64_t n = 0;
     const int rc = border_pack_impl(c, d_all_keys, counts, stride, world, rank, d_send, cap_rows,
-                                    send_counts, false, d_send ? &rows : nullptr, &n);
+                                    send_counts);
     if (rc) return rc;
-    if (d_send) {
-        c->brd_open = true;
-        c->brd_sent = rows;
-        c->brd_n_sent = n;
-    }
+    if (d_send) c->brd_open = true;
     return TSDF_OK;
 }
 
@@ -2846,18 +2813,13 @@ int tsdf_border_merge_device(tsdf_ctx* c, const uint32_t* d_recv, const uint64_t
     if (!d_recv) return fail(c, TSDF_EINVAL, "null tile buffer");
     int rc = drain(c);
     if (rc) return rc;
+    Scratch tmp;
     uint32_t* bk = nullptr;
-    HIPCHK(c, hipMalloc(&bk, total * TSDF_TILE_WORDS * 4));
+    HIPCHK(c, tmp.get(c, &bk, total * TSDF_TILE_WORDS));
     // the backup joins the abort's restore list only once its snapshot is launched (a
     // failed launch left uninitialised rows for the restore to write over held bricks)
-    {
-        const hipError_t e = launch_border_snapshot(c->T, c->Pl, d_recv, total, bk, c->stream);
-        if (e != hipSuccess) {
-            (void)hipFree(bk);
-            return fail(c, TSDF_EHIP, "border snapshot: %s", hipGetErrorString(e));
-        }
-    }
-    c->brd_backup.push_back({bk, total});
+    HIPCHK(c, launch_border_snapshot(c->T, c->Pl, d_recv, total, bk, c->stream));
+    c->brd_backup.push_back({tmp.take(bk), total});
     uint64_t row = 0;
     for (uint32_t r = 0; r < world; r++) {  // sources in ascending rank order
         if (recv_counts[r])
@@ -2902,8 +2864,7 @@ int tsdf_border_commit_device(tsdf_ctx* c, int32_t commit) {
 
 int tsdf_create_sharded(const tsdf_params* p, uint32_t n, const int32_t* device_ids, tsdf_ctx** out) {
     if (!p || !out || n == 0 || n > TSDF_MAX_WORLD) return TSDF_EINVAL;
-    int dev0 = 0;
-    if (hipGetDevice(&dev0) != hipSuccess) dev0 = -1;  // the caller's device, restored at the end
+    DeviceGuard caller;  // the caller's device as it was
     for (uint32_t k = 0; k < n; k++) out[k] = nullptr;
     int rc = TSDF_OK;
     for (uint32_t k = 0; k < n && rc == TSDF_OK; k++) {
@@ -2937,46 +2898,8 @@ int tsdf_create_sharded(const tsdf_params* p, uint32_t n, const int32_t* device_
             (void)hipGetLastError();  // an already-enabled pair leaves its error code behind
         }
     }
-    if (dev0 >= 0) (void)hipSetDevice(dev0);  // the caller's device as it was
     return rc;
 }
-
-}  // extern "C"
-
-// Tiles of `rows` rows from context src's device buffer to context dst's (xGMI peer copy, or a
-// device copy when both share a GPU)
-static hipError_t copy_tiles(tsdf_ctx* dst, uint32_t* d_dst, tsdf_ctx* src, const uint32_t* d_src,
-                             uint64_t rows) {
-    const size_t bytes = rows * TSDF_TILE_WORDS * 4;
-    if (!bytes) return hipSuccess;
-    return src->device == dst->device ? hipMemcpy(d_dst, d_src, bytes, hipMemcpyDeviceToDevice)
-                                      : hipMemcpyPeer(d_dst, dst->device, d_src, src->device, bytes);
-}
-
-// Device buffers of several contexts, freed on their devices at scope end.
-struct DevBufs {
-    std::vector<std::pair<int, void*>> v;
-    int get(tsdf_ctx* c, size_t bytes, void** p) {
-        HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipMalloc(p, std::max<size_t>(bytes, 16)));
-        v.push_back({c->device, *p});
-        return TSDF_OK;
-    }
-    ~DevBufs() {
-        for (auto& q : v) {
-            (void)hipSetDevice(q.first);
-            (void)hipFree(q.second);
-        }
-    }
-};
-
-// A failure in a multi-context call: the failing context holds the message, the first gets a copy
-static int first_error(tsdf_ctx* const* ctxs, uint32_t n, int rc) {
-    for (uint32_t k = 1; k < n && ctxs[0]->err.empty(); k++) ctxs[0]->err = ctxs[k]->err;
-    return rc;
-}
-
-extern "C" {
 
 // The border reduce of tsdf_brick_keys_device / tsdf_border_pack_device / tsdf_border_merge_device
 // among the contexts of one process: the keys meet on the host, and each source's tiles go to
@@ -2986,91 +2909,85 @@ extern "C" {
 // are the sent bricks reset (commit), otherwise every context is rolled back (abort), so a failed
 // reduce neither loses nor double-counts mass.  Synchronous.
 int tsdf_border_reduce_local(tsdf_ctx* const* ctxs, uint32_t n, uint64_t* bricks_moved) {
-    if (!ctxs || n == 0 || n > TSDF_MAX_WORLD) return TSDF_EINVAL;
-    for (uint32_t k = 0; k < n; k++)
-        if (!ctxs[k]) return TSDF_EINVAL;
+    if (!ctxs_ok(ctxs, n)) return TSDF_EINVAL;
     if (bricks_moved) *bricks_moved = 0;
     if (n == 1) return TSDF_OK;
     for (uint32_t k = 0; k < n; k++)
         if (border_busy(ctxs[k])) return first_error(ctxs, n, TSDF_EINVAL);
-    int dev0 = 0;
-    if (hipGetDevice(&dev0) != hipSuccess) dev0 = -1;
+    DeviceGuard caller;  // (restored after the buffers are freed on their devices)
+    Scratch bufs;
     int rc = TSDF_OK;
-    {
-        DevBufs bufs;
-        // 1. every context's keys, gathered on the host
-        std::vector<uint64_t> counts(n, 0);
-        std::vector<std::vector<uint64_t>> hkeys(n);
-        for (uint32_t k = 0; k < n && !rc; k++) {
-            tsdf_ctx* c = ctxs[k];
-            uint64_t nb = 0;
-            rc = pool_bricks(c, &nb);
-            void* d = nullptr;
-            if (!rc) rc = bufs.get(c, nb * 8, &d);
-            if (!rc) rc = tsdf_brick_keys_device(c, static_cast<uint64_t*>(d), nb, &counts[k]);
-            if (!rc) {
-                hkeys[k].resize(counts[k]);
-                if (counts[k] &&
-                    hipMemcpy(hkeys[k].data(), d, counts[k] * 8, hipMemcpyDeviceToHost) != hipSuccess)
-                    rc = fail(c, TSDF_EHIP, "border reduce: key read-back failed");
-            }
+    // 1. every context's keys, gathered on the host
+    std::vector<uint64_t> counts(n, 0);
+    std::vector<std::vector<uint64_t>> hkeys(n);
+    for (uint32_t k = 0; k < n && !rc; k++) {
+        tsdf_ctx* c = ctxs[k];
+        uint64_t nb = 0;
+        rc = pool_bricks(c, &nb);
+        uint64_t* d = nullptr;
+        if (!rc) rc = bufs.get_or_fail(c, &d, nb);
+        if (!rc) rc = tsdf_brick_keys_device(c, d, nb, &counts[k]);
+        if (!rc) {
+            hkeys[k].resize(counts[k]);
+            if (counts[k] &&
+                hipMemcpy(hkeys[k].data(), d, counts[k] * 8, hipMemcpyDeviceToHost) != hipSuccess)
+                rc = fail(c, TSDF_EHIP, "border reduce: key read-back failed");
         }
-        uint64_t stride = 1;
-        for (uint32_t k = 0; k < n; k++) stride = std::max(stride, counts[k]);
-        std::vector<uint64_t> all(stride * n, ~0ull);
-        for (uint32_t k = 0; k < n; k++)
-            std::copy(hkeys[k].begin(), hkeys[k].end(), all.begin() + k * stride);
-        // 2. each context packs the bricks a lower rank owns (no reset: the transaction)
-        std::vector<uint32_t*> send(n, nullptr);
-        std::vector<std::vector<uint64_t>> sc(n, std::vector<uint64_t>(n, 0));
-        for (uint32_t k = 0; k < n && !rc; k++) {
-            tsdf_ctx* c = ctxs[k];
-            void *dk = nullptr, *ds = nullptr;
-            rc = bufs.get(c, all.size() * 8, &dk);
-            if (!rc && hipMemcpy(dk, all.data(), all.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
-                rc = fail(c, TSDF_EHIP, "border reduce: key upload failed");
-            if (!rc) rc = bufs.get(c, counts[k] * TSDF_TILE_WORDS * 4, &ds);
-            if (!rc)
-                rc = tsdf_border_pack_device(c, static_cast<uint64_t*>(dk), counts.data(), stride, n,
-                                             k, static_cast<uint32_t*>(ds), counts[k], sc[k].data());
-            send[k] = static_cast<uint32_t*>(ds);
-        }
-        // 3. every owner d receives block d of every source, sources ascending; 4. merge
-        uint64_t moved = 0;
-        for (uint32_t d = 0; d < n && !rc; d++) {
-            tsdf_ctx* c = ctxs[d];
-            std::vector<uint64_t> rcnt(n, 0);
-            uint64_t total = 0;
-            for (uint32_t r = 0; r < n; r++) {
-                rcnt[r] = sc[r][d];
-                total += rcnt[r];
-            }
-            if (!total) continue;
-            void* dr = nullptr;
-            rc = bufs.get(c, total * TSDF_TILE_WORDS * 4, &dr);
-            uint64_t row = 0;
-            for (uint32_t r = 0; r < n && !rc; r++) {
-                if (!rcnt[r]) continue;
-                uint64_t off = 0;
-                for (uint32_t q = 0; q < d; q++) off += sc[r][q];
-                const hipError_t e = copy_tiles(c, static_cast<uint32_t*>(dr) + row * TSDF_TILE_WORDS,
-                                                ctxs[r], send[r] + off * TSDF_TILE_WORDS, rcnt[r]);
-                if (e != hipSuccess)
-                    rc = fail(c, TSDF_EHIP, "border reduce: tile copy: %s", hipGetErrorString(e));
-                row += rcnt[r];
-            }
-            if (!rc) rc = tsdf_border_merge_device(c, static_cast<uint32_t*>(dr), rcnt.data(), n);
-            moved += total;
-        }
-        // 5. commit everywhere when everything succeeded, else roll every context back
-        const int commit = rc == TSDF_OK ? 1 : 0;
-        for (uint32_t k = 0; k < n; k++) {
-            const int crc = tsdf_border_commit_device(ctxs[k], commit);
-            if (crc && !rc) rc = crc;
-        }
-        if (!rc && bricks_moved) *bricks_moved = moved;
     }
-    if (dev0 >= 0) (void)hipSetDevice(dev0);
+    uint64_t stride = 1;
+    for (uint32_t k = 0; k < n; k++) stride = std::max(stride, counts[k]);
+    std::vector<uint64_t> all(stride * n, ~0ull);
+    for (uint32_t k = 0; k < n; k++)
+        std::copy(hkeys[k].begin(), hkeys[k].end(), all.begin() + k * stride);
+    // 2. each context packs the bricks a lower rank owns (no reset: the transaction)
+    std::vector<uint32_t*> send(n, nullptr);
+    std::vector<std::vector<uint64_t>> sc(n, std::vector<uint64_t>(n, 0));
+    for (uint32_t k = 0; k < n && !rc; k++) {
+        tsdf_ctx* c = ctxs[k];
+        uint64_t* dk = nullptr;
+        rc = bufs.get_or_fail(c, &dk, all.size());
+        if (!rc && hipMemcpy(dk, all.data(), all.size() * 8, hipMemcpyHostToDevice) != hipSuccess)
+            rc = fail(c, TSDF_EHIP, "border reduce: key upload failed");
+        if (!rc) rc = bufs.get_or_fail(c, &send[k], counts[k] * TSDF_TILE_WORDS);
+        if (!rc)
+            rc = tsdf_border_pack_device(c, dk, counts.data(), stride, n, k, send[k], counts[k],
+                                         sc[k].data());
+    }
+    // 3. every owner d receives block d of every source, sources ascending; 4. merge
+    uint64_t moved = 0;
+    for (uint32_t d = 0; d < n && !rc; d++) {
+        tsdf_ctx* c = ctxs[d];
+        std::vector<uint64_t> rcnt(n, 0);
+        uint64_t total = 0;
+        for (uint32_t r = 0; r < n; r++) {
+            rcnt[r] = sc[r][d];
+            total += rcnt[r];
+        }
+        if (!total) continue;
+        uint32_t* dr = nullptr;
+        rc = bufs.get_or_fail(c, &dr, total * TSDF_TILE_WORDS);
+        uint64_t row = 0;
+        for (uint32_t r = 0; r < n && !rc; r++) {
+            if (!rcnt[r]) continue;
+            uint64_t off = 0;
+            for (uint32_t q = 0; q < d; q++) off += sc[r][q];
+            const hipError_t e = copy_between(c, dr + row * TSDF_TILE_WORDS, ctxs[r],
+                                              send[r] + off * TSDF_TILE_WORDS,
+                                              rcnt[r] * TSDF_TILE_WORDS * 4);
+            if (e != hipSuccess)
+                rc = fail(c, TSDF_EHIP, "border reduce: tile copy: %s", hipGetErrorString(e));
+            row += rcnt[r];
+        }
+        if (!rc) rc = tsdf_border_merge_device(c, dr, rcnt.data(), n);
+        moved += total;
+    }
+    // 5. commit everywhere when everything succeeded, else roll every context back
+    const int commit = rc == TSDF_OK ? 1 : 0;
+    for (uint32_t k = 0; k < n; k++) {
+        const int crc = tsdf_border_commit_device(ctxs[k], commit);
+        if (crc && !rc) rc = crc;
+    }
+    if (!rc && bricks_moved) *bricks_moved = moved;
     return rc ? first_error(ctxs, n, rc) : TSDF_OK;
 }
 
@@ -3089,32 +3006,18 @@ int tsdf_halo_keys_device(tsdf_ctx* c, uint64_t* d_keys, uint64_t cap, uint64_t*
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<uint64_t> keys(nb);
     std::vector<uint32_t> obs(nb);
+    Scratch tmp;
     uint32_t* d_obs = nullptr;
-    hipError_t e = hipMalloc(&d_obs, nb * 4);
-    if (e == hipSuccess) e = launch_brick_observed(c->Pl, (uint32_t)nb, d_obs, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(obs.data(), d_obs, nb * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(keys.data(), c->T.brick_keys, nb * 8, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (d_obs) (void)hipFree(d_obs);
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "halo keys: %s", hipGetErrorString(e));
+    HIPCHK(c, tmp.get(c, &d_obs, nb));
+    HIPCHK(c, launch_brick_observed(c->Pl, (uint32_t)nb, d_obs, c->stream));
+    HIPCHK(c, hipMemcpyAsync(obs.data(), d_obs, nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(keys.data(), c->T.brick_keys, nb * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<uint64_t> have;
     for (uint64_t i = 0; i < nb; i++)
         if (obs[i]) have.push_back(keys[i]);
     std::sort(have.begin(), have.end());
-    std::vector<uint64_t> need;
-    for (uint64_t k : have) {
-        const int64_t bx = (int64_t)(k & 0x1FFFFF), by = (int64_t)((k >> 21) & 0x1FFFFF),
-                      bz = (int64_t)((k >> 42) & 0x1FFFFF);
-        for (int d = 1; d < 8; d++) {
-            const int64_t nx = bx + (d & 1), ny = by + ((d >> 1) & 1), nz = bz + (d >> 2);
-            if (nx > 0x1FFFFF || ny > 0x1FFFFF || nz > 0x1FFFFF) continue;
-            const uint64_t q = (uint64_t)nx | ((uint64_t)ny << 21) | ((uint64_t)nz << 42);
-            if (!std::binary_search(have.begin(), have.end(), q)) need.push_back(q);
-        }
-    }
-    std::sort(need.begin(), need.end());
-    need.erase(std::unique(need.begin(), need.end()), need.end());
+    const std::vector<uint64_t> need = brick_halo_needed(have);
     *n_out = need.size();
     if (need.size() > cap)
         return fail(c, TSDF_EOVERFLOW, "halo keys need %llu entries", (unsigned long long)need.size());
@@ -3137,17 +3040,15 @@ int tsdf_halo_pack_device(tsdf_ctx* c, const uint64_t* d_req, uint64_t n_req, ui
     int rc = drain(c);
     if (rc) return rc;
     HIPCHK(c, hipSetDevice(c->device));
+    Scratch tmp;
     uint32_t* d_n = nullptr;
     uint32_t nr = 0;
-    hipError_t e = hipMalloc(&d_n, 4);
-    if (e == hipSuccess) e = hipMemsetAsync(d_n, 0, 4, c->stream);
-    if (e == hipSuccess)
-        e = launch_halo_pack(c->T, c->Pl, d_req, (uint32_t)n_req, d_send, (uint32_t)cap_rows, d_n,
-                             c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&nr, d_n, 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (d_n) (void)hipFree(d_n);
-    if (e != hipSuccess) return fail(c, TSDF_EHIP, "halo pack: %s", hipGetErrorString(e));
+    HIPCHK(c, tmp.get(c, &d_n, 1));
+    HIPCHK(c, hipMemsetAsync(d_n, 0, 4, c->stream));
+    HIPCHK(c, launch_halo_pack(c->T, c->Pl, d_req, (uint32_t)n_req, d_send, (uint32_t)cap_rows, d_n,
+                               c->stream));
+    HIPCHK(c, hipMemcpyAsync(&nr, d_n, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     *n_rows = nr;
     if (nr > cap_rows) return fail(c, TSDF_EOVERFLOW, "halo pack needs %u rows", nr);
     return TSDF_OK;
@@ -3166,75 +3067,64 @@ int tsdf_extract_mesh_halo(tsdf_ctx* c, float min_weight, int32_t table, const u
 // context; tri holds the contexts' soups one after another in context order (tri == NULL: count).
 int tsdf_extract_mesh_local(tsdf_ctx* const* ctxs, uint32_t n, float min_weight, int32_t table,
                             float* tri, uint64_t cap, uint64_t* n_tri) {
-    if (!ctxs || n == 0 || n > TSDF_MAX_WORLD || !n_tri) return TSDF_EINVAL;
-    for (uint32_t k = 0; k < n; k++)
-        if (!ctxs[k]) return TSDF_EINVAL;
+    if (!ctxs_ok(ctxs, n) || !n_tri) return TSDF_EINVAL;
     *n_tri = 0;
     if (n == 1) return tsdf_extract_mesh_table(ctxs[0], min_weight, table, tri, cap, n_tri);
     int rc = tsdf_border_reduce_local(ctxs, n, nullptr);
     if (rc) return rc;
-    int dev0 = 0;
-    if (hipGetDevice(&dev0) != hipSuccess) dev0 = -1;
-    {
-        DevBufs bufs;
-        // every context's requests
-        std::vector<void*> req(n, nullptr);
-        std::vector<uint64_t> nreq(n, 0);
-        for (uint32_t k = 0; k < n && !rc; k++) {
-            rc = tsdf_halo_keys_device(ctxs[k], nullptr, 0, &nreq[k]);
-            if (rc == TSDF_EOVERFLOW) rc = TSDF_OK;
-            if (!rc) rc = bufs.get(ctxs[k], nreq[k] * 8, &req[k]);
-            uint64_t got = 0;
-            if (!rc) rc = tsdf_halo_keys_device(ctxs[k], static_cast<uint64_t*>(req[k]), nreq[k], &got);
-        }
-        // holder j packs for requester k on j's GPU; the tiles go to k's halo buffer
-        std::vector<void*> halo(n, nullptr);
-        std::vector<uint64_t> nh(n, 0);
-        for (uint32_t k = 0; k < n && !rc; k++) {
-            if (!nreq[k]) continue;
-            rc = bufs.get(ctxs[k], nreq[k] * TSDF_TILE_WORDS * 4, &halo[k]);
-            for (uint32_t j = 0; j < n && !rc; j++) {
-                if (j == k) continue;
-                void *dq = nullptr, *ds = nullptr;
-                rc = bufs.get(ctxs[j], nreq[k] * 8, &dq);
-                if (!rc) {
-                    const hipError_t e =
-                        ctxs[j]->device == ctxs[k]->device
-                            ? hipMemcpy(dq, req[k], nreq[k] * 8, hipMemcpyDeviceToDevice)
-                            : hipMemcpyPeer(dq, ctxs[j]->device, req[k], ctxs[k]->device, nreq[k] * 8);
-                    if (e != hipSuccess)
-                        rc = fail(ctxs[j], TSDF_EHIP, "halo: key copy: %s", hipGetErrorString(e));
-                }
-                if (!rc) rc = bufs.get(ctxs[j], nreq[k] * TSDF_TILE_WORDS * 4, &ds);
-                uint64_t rows = 0;
-                if (!rc)
-                    rc = tsdf_halo_pack_device(ctxs[j], static_cast<uint64_t*>(dq), nreq[k],
-                                               static_cast<uint32_t*>(ds), nreq[k] - nh[k], &rows);
-                if (!rc) {
-                    const hipError_t e = copy_tiles(
-                        ctxs[k], static_cast<uint32_t*>(halo[k]) + nh[k] * TSDF_TILE_WORDS, ctxs[j],
-                        static_cast<uint32_t*>(ds), rows);
-                    if (e != hipSuccess)
-                        rc = fail(ctxs[k], TSDF_EHIP, "halo: tile copy: %s", hipGetErrorString(e));
-                }
-                nh[k] += rows;
-            }
-        }
-        // one mesh per context, soups concatenated
-        uint64_t total = 0;
-        for (uint32_t k = 0; k < n && !rc; k++) {
-            uint64_t nt = 0;
-            float* out = tri && total <= cap ? tri + 9 * total : nullptr;
-            rc = mesh_impl(ctxs[k], min_weight, table, static_cast<uint32_t*>(halo[k]), nh[k], out,
-                           tri && total <= cap ? cap - total : 0, &nt);
-            if (rc == TSDF_EOVERFLOW) rc = TSDF_OK;  // the total decides below
-            total += nt;
-        }
-        *n_tri = total;
-        if (!rc && tri && total > cap)
-            rc = fail(ctxs[0], TSDF_EOVERFLOW, "mesh has %llu triangles", (unsigned long long)total);
+    DeviceGuard caller;  // (restored after the buffers are freed on their devices)
+    Scratch bufs;
+    // every context's requests
+    std::vector<uint64_t*> req(n, nullptr);
+    std::vector<uint64_t> nreq(n, 0);
+    for (uint32_t k = 0; k < n && !rc; k++) {
+        rc = tsdf_halo_keys_device(ctxs[k], nullptr, 0, &nreq[k]);
+        if (rc == TSDF_EOVERFLOW) rc = TSDF_OK;
+        if (!rc) rc = bufs.get_or_fail(ctxs[k], &req[k], nreq[k]);
+        uint64_t got = 0;
+        if (!rc) rc = tsdf_halo_keys_device(ctxs[k], req[k], nreq[k], &got);
     }
-    if (dev0 >= 0) (void)hipSetDevice(dev0);
+    // holder j packs for requester k on j's GPU; the tiles go to k's halo buffer
+    std::vector<uint32_t*> halo(n, nullptr);
+    std::vector<uint64_t> nh(n, 0);
+    for (uint32_t k = 0; k < n && !rc; k++) {
+        if (!nreq[k]) continue;
+        rc = bufs.get_or_fail(ctxs[k], &halo[k], nreq[k] * TSDF_TILE_WORDS);
+        for (uint32_t j = 0; j < n && !rc; j++) {
+            if (j == k) continue;
+            uint64_t* dq = nullptr;
+            uint32_t* ds = nullptr;
+            rc = bufs.get_or_fail(ctxs[j], &dq, nreq[k]);
+            if (!rc) {
+                const hipError_t e = copy_between(ctxs[j], dq, ctxs[k], req[k], nreq[k] * 8);
+                if (e != hipSuccess)
+                    rc = fail(ctxs[j], TSDF_EHIP, "halo: key copy: %s", hipGetErrorString(e));
+            }
+            if (!rc) rc = bufs.get_or_fail(ctxs[j], &ds, nreq[k] * TSDF_TILE_WORDS);
+            uint64_t rows = 0;
+            if (!rc) rc = tsdf_halo_pack_device(ctxs[j], dq, nreq[k], ds, nreq[k] - nh[k], &rows);
+            if (!rc) {
+                const hipError_t e = copy_between(ctxs[k], halo[k] + nh[k] * TSDF_TILE_WORDS, ctxs[j],
+                                                  ds, rows * TSDF_TILE_WORDS * 4);
+                if (e != hipSuccess)
+                    rc = fail(ctxs[k], TSDF_EHIP, "halo: tile copy: %s", hipGetErrorString(e));
+            }
+            nh[k] += rows;
+        }
+    }
+    // one mesh per context, soups concatenated
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n && !rc; k++) {
+        uint64_t nt = 0;
+        float* out = tri && total <= cap ? tri + 9 * total : nullptr;
+        rc = mesh_impl(ctxs[k], min_weight, table, halo[k], nh[k], out,
+                       tri && total <= cap ? cap - total : 0, &nt);
+        if (rc == TSDF_EOVERFLOW) rc = TSDF_OK;  // the total decides below
+        total += nt;
+    }
+    *n_tri = total;
+    if (!rc && tri && total > cap)
+        rc = fail(ctxs[0], TSDF_EOVERFLOW, "mesh has %llu triangles", (unsigned long long)total);
     return rc ? first_error(ctxs, n, rc) : TSDF_OK;
 }
 
