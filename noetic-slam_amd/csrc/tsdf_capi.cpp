@@ -24,6 +24,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../../include/tsdf_hip.h"
@@ -31,6 +32,7 @@
 #include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
 #include "brick_key.h"
+#include "ctx_plan.h"
 #include "host_pack.h"
 #include "pack_pool.h"
 #include "tsdf_device.h"
@@ -45,6 +47,11 @@ static_assert(BRICK_KEY_BIAS == BRICK_COORD_BIAS, "host and device brick keys di
 namespace {
 
 // Diagnostic host timing of launch() sections (TSDF_HOST_TIMING=1: averages printed at destroy).
+// launch()'s slots, by the number the stderr line prints them under (2 and 11: unused, 0.00):
+enum HtSlot {
+    HT_PRE = 0, HT_WAITS = 1, HT_FRONT = 3, HT_COMPACT = 4, HT_BACK = 5, HT_INTEGRATE = 6,
+    HT_FINISH = 7, HT_RING_WAIT = 8, HT_RING_COPY = 9, HT_UPLOAD = 10
+};
 struct HostTiming {
     bool on = std::getenv("TSDF_HOST_TIMING") != nullptr;
     double acc[12] = {};
@@ -172,49 +179,123 @@ void sector_bounds(double yaw0, uint32_t sector, uint32_t n, RayConst& R) {
     R.sec_wrap = R.sec_hi <= R.sec_lo ? 1 : 0;
 }
 
-// The smallest double x >= 0 with (float)sqrt(x) >= tau (bisection over the ordered bit patterns
-// of non-negative doubles): behind the hit, VDBFusion's gate -(float)dist > -tau holds iff
-// d2 < this threshold (TSDF_SEM_VDBFUSION_F64; the oracle gates on the sqrt itself).
-double gate_threshold(float tau) {
-    auto ok = [&](uint64_t b) {
-        double x;
-        std::memcpy(&x, &b, 8);
-        return (float)std::sqrt(x) >= tau;
-    };
-    double hi_d = 4.0 * (double)tau * (double)tau + 1.0;
-    uint64_t lo = 0, hi;
-    std::memcpy(&hi, &hi_d, 8);
-    while (hi - lo > 1) {  // ok(lo) false, ok(hi) true
-        const uint64_t mid = lo + (hi - lo) / 2;
-        if (ok(mid)) hi = mid;
-        else lo = mid;
+// ---- the owners of a context's HIP resources -------------------------------------
+
+// A device or pinned buffer, an event, a stream: each frees what it holds when it is destroyed,
+// reset or assigned over, and an empty one frees nothing, so a half-built context tears down like
+// a whole one.  They convert to the raw handle: the kernels' argument structs (Table, Pool, Work,
+// MgBufs) are views filled from them (set_views).
+template <class T, bool PINNED>
+struct HipBuf {
+    T* p = nullptr;
+    HipBuf() = default;
+    explicit HipBuf(T* q) : p(q) {}
+    HipBuf(HipBuf&& o) noexcept : p(std::exchange(o.p, nullptr)) {}
+    HipBuf& operator=(HipBuf&& o) noexcept {
+        if (this != &o) reset(std::exchange(o.p, nullptr));
+        return *this;
     }
-    double x;
-    std::memcpy(&x, &hi, 8);
-    return x;
-}
+    ~HipBuf() { reset(); }
+    void reset(T* q = nullptr) {
+        if (p) (void)(PINNED ? hipHostFree(p) : hipFree(p));
+        p = q;
+    }
+    // a fresh allocation of `bytes` bytes (the owner must be empty)
+    hipError_t alloc_bytes(size_t bytes) {
+        return PINNED ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+    }
+    hipError_t alloc(size_t n) { return alloc_bytes(n * sizeof(T)); }
+    operator T*() const { return p; }
+    T* operator->() const { return p; }
+};
+template <class T> using DevBuf = HipBuf<T, false>;
+template <class T> using PinBuf = HipBuf<T, true>;
+
+// An event without timing (the contexts order streams with them; EventTimer keeps its own) and a
+// non-blocking stream
+template <class H, hipError_t (*MAKE)(H*, unsigned), unsigned FLAGS, hipError_t (*KILL)(H)>
+struct HipHandle {
+    H h = nullptr;
+    HipHandle() = default;
+    HipHandle(const HipHandle&) = delete;
+    HipHandle& operator=(const HipHandle&) = delete;
+    ~HipHandle() { if (h) (void)KILL(h); }
+    hipError_t create() { return MAKE(&h, FLAGS); }
+    operator H() const { return h; }
+};
+using Event = HipHandle<hipEvent_t, hipEventCreateWithFlags, hipEventDisableTiming, hipEventDestroy>;
+using Stream = HipHandle<hipStream_t, hipStreamCreateWithFlags, hipStreamNonBlocking, hipStreamDestroy>;
+
+
+// The capacity-dependent buffers: brick pool, hash table, and per batch parity the cells and the
+// per-brick work lists.  The context holds the installed one; growth builds a
+// second and move-assigns it over the first, which frees the old buffers.
+struct Capacity {
+    uint64_t max_bricks = 0, cap = 0;
+    uint32_t max_active = 0;
+    DevBuf<uint64_t> keys, brick_keys;
+    DevBuf<uint32_t> slots, touched, cell[2];  // (u64 cells with the single walk)
+    DevBuf<float> sdf, weight;
+    DevBuf<uint4> active[2], active_ord[2], cagg[2];
+};
+
+// One batch parity's capacity-independent buffers: the work lists (Work), sized by the plan and,
+// for fb / smp / spn, doubled on overflow (grow_list), and the merged pre-pass' set (MgBufs;
+// Voxblox MergedTsdfIntegrator only, tsdf_merged.hip)
+struct Lane {
+    DevBuf<uint32_t> pair, blk_n, plan, spn, ord_hist, act, rsv_n;  // (rsv, rsv_n: TSDF_CNT_SPLIT)
+    DevBuf<uint4> blk, fb, rsv;
+    DevBuf<uint2> smp;
+    DevBuf<uint64_t> mg_ekey;
+    DevBuf<uint32_t> mg_eidx, mg_bcnt, mg_bst, mg_bscan;
+    DevBuf<float> mg_xyz, mg_w;
+};
+
+// Batch records for the kernels: a pinned host ring and its device twin (launch() copies a batch's
+// n_scans + 1 records into the next slot on the batch's stream), one event per slot
+struct ScanRing {
+    static constexpr int N = 16;
+    PinBuf<ScanRec> host;
+    DevBuf<ScanRec> dev;
+    const ScanRec* host_dev = nullptr;  // `host` as the device addresses it (k_upload)
+    // ring progress: k_upload of launch q stores q + 1 here once it has read its slot
+    PinBuf<unsigned long long> done;
+    unsigned long long* done_dev = nullptr;
+    Event ev[N];
+    uint64_t next = 0;
+
+    hipError_t create() {
+        hipError_t e = host.alloc((size_t)N * (MAX_BATCH + 1));
+        if (e == hipSuccess) e = dev.alloc((size_t)N * (MAX_BATCH + 1));
+        void* dp = nullptr;
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&dp, host, 0);
+        host_dev = static_cast<const ScanRec*>(dp);
+        if (e == hipSuccess) e = done.alloc_bytes(64);
+        if (e == hipSuccess) *done = 0;
+        if (e == hipSuccess) e = hipHostGetDevicePointer(&dp, done, 0);
+        done_dev = static_cast<unsigned long long*>(dp);
+        for (int k = 0; k < N && e == hipSuccess; k++) e = ev[k].create();
+        return e;
+    }
+};
 
 }  // namespace
 
 struct tsdf_ctx {
     tsdf_params p{};
     int device = -1;
-    hipStream_t stream = nullptr;
+    Stream stream;
     RayConst R{};
+    // what the kernels take: views of the owners below (set_views)
     Table T{};
     Pool Pl{};
-    Work Wk{};
-    Globals* G = nullptr;
-    uint64_t cap = 0;
+    Work W2[2]{};
+    MgBufs mg[2];
+    DevBuf<Globals> G;
     uint64_t max_points = 0;  // per scan
     uint32_t max_batch = 0;
-    uint64_t batch_points = 0;  // pair-slot capacity / maxp: points one batch may hold
-    uint32_t max_blocks = 0;    // k_count / k_place workgroups one batch may need
-    uint64_t slots = 0;         // pair slots of one batch
-    // single walk: k_walk + k_spans instead of k_count + k_place, when asked for
-    // (tsdf_params.walk) and the band's walk fits nstep register slots per ray
-    bool fused = false;
-    int nstep = 0;
+    CtxPlan plan;  // one batch's sizes (ctx_plan.h), as created
+    uint32_t max_fb = 0, max_smp = 0, max_spn = 0;  // the growable lists' entries now (grow_list)
     // batches of at most small_ns scans take k_integrate_small (TSDF_SMALL_NS; 0: never; measured
     // break-even with k_integrate at 6 scans)
     int small_ns = 5;
@@ -225,20 +306,19 @@ struct tsdf_ctx {
     // (bit-exact, ~29% fewer cell atomics, but measured slower: DESIGN.md §10, round 4)
     bool count_paired = false;
     // host-pointer path: pinned double buffer per scan; the pending batch's points are staged in
-    // stage2[batch parity]
-    float* h_stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_done[2] = {nullptr, nullptr};
+    // stage2[pend_stage]
+    PinBuf<float> h_stage[2];
+    Event stage_done[2];
     int stage_cur = 0;
-    // Batch pipeline: batch b runs on bst[b & 1] with its own work buffers (W2), per-scan cells
-    // (cell2) and device staging (stage2), so batch b + 1's count / compact / place overlap batch
-    // b's place / integrate.  Cross-batch order: k_count(b+1) after k_compact(b)
-    // (the table's `touched` words), k_integrate(b+1) after k_finish(b) (per-brick fuse order).
-    hipStream_t bst[2] = {nullptr, nullptr};
-    Work W2[2]{};
-    uint32_t* cell2[2] = {nullptr, nullptr};  // u64 cells with the single walk
-    float* stage2[2] = {nullptr, nullptr};
-    hipEvent_t ev_main = nullptr;
-    hipEvent_t ev_compact[2] = {nullptr, nullptr};
+    // Batch pipeline: batch b runs on bst[b & 1] with its own work buffers (lane, W2), per-scan
+    // cells (K.cell) and device staging (stage2), so batch b + 1's count / compact / place overlap
+    // batch b's place / integrate.  Cross-batch order: the table above launch() and DESIGN.md §5.
+    Stream bst[2];
+    Capacity K;  // the installed capacity
+    Lane lane[2];
+    DevBuf<float> stage2[2];
+    Event ev_main;
+    Event ev_compact[2];
     // the end of the last batch of each parity: the ring event of that batch's slot (one marker
     // per batch; every marker in the stream costs the GPU a few microseconds)
     hipEvent_t ev_integ[2] = {nullptr, nullptr};
@@ -248,19 +328,9 @@ struct tsdf_ctx {
     int pend_stage = 0;
     int last_stage = 1;  // the buffer of the most recently launched host batch
     uint64_t stage_reader[2] = {~0ull, ~0ull};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    // batch records for the kernels: a pinned host ring and its device twin (launch() copies a
-    // batch's n_scans + 1 records into the next slot on the batch's stream)
-    static constexpr int RING = 16;
+    Event stage_ev[2];
+    ScanRing ring;
     HostTiming ht;
-    ScanRec* h_ring = nullptr;
-    ScanRec* d_ring = nullptr;
-    const ScanRec* d_ring_src = nullptr;  // h_ring as the device addresses it (k_upload)
-    // ring progress: k_upload of launch q stores q + 1 here once it has read its slot
-    unsigned long long* h_ring_done = nullptr;
-    unsigned long long* d_ring_done = nullptr;
-    hipEvent_t ring_ev[RING] = {};
-    uint64_t ring_next = 0;
     uint64_t batch_id = 0;
     uint64_t n_scans = 0, n_batches = 0, n_points_in = 0;
     EventTimer* timer = nullptr;
@@ -284,17 +354,15 @@ struct tsdf_ctx {
     std::vector<int8_t> split_sec;
     HostTiming split_ht;  // TSDF_HOST_TIMING: prep, classify, scatter, copies + queue (us/scan)
     uint64_t n_grows = 0, n_replayed = 0;
-    // Voxblox MergedTsdfIntegrator (tsdf_params.voxblox_method): the bundling pre-pass' buffers,
-    // one set per batch parity (tsdf_merged.hip)
+    // Voxblox MergedTsdfIntegrator (tsdf_params.voxblox_method): the bundling pre-pass runs first
     bool merged = false;
     // TSDF_SECTOR_RULE_INDEX sharding (ABI v10): the context takes points [share_lo, share_hi) of
     // every cloud (idx_share); the kernels' azimuth filter is off (R.sec_on = 0)
     bool idx_rule = false;
-    MgBufs mg[2];
     // tsdf_create_sharded: the contexts whose device memory this one reaches directly (peer access
     // or the same device); tsdf_integrate_sectors' fan-out: its copy-done event (this device)
     uint64_t peer_mask = 0;
-    hipEvent_t bc_ev = nullptr;
+    Event bc_ev;
     // tsdf_integrate_sectors' fan-out, batch-granular: a follower's pending points [fan_lo, fan_hi)
     // are still in its leader's staging buffer fan_buf (same offsets: the contexts' batches run in
     // lockstep) and are copied in ONE device-to-device copy before the follower's batch launches
@@ -307,12 +375,12 @@ struct tsdf_ctx {
     // (reset at commit) and, per merge, the received bricks' pre-merge tiles (written back at
     // abort).  While a reduce is open the context takes no scan and no import.
     bool brd_open = false;
-    uint32_t* brd_sent = nullptr;
+    DevBuf<uint32_t> brd_sent;
     uint64_t brd_n_sent = 0;
-    std::vector<std::pair<uint32_t*, uint64_t>> brd_backup;
+    std::vector<std::pair<DevBuf<uint32_t>, uint64_t>> brd_backup;
     // tsdf_align_terms_device's workgroup partials and their sum (launch_align), allocated at the
     // first call
-    double* align_part = nullptr;
+    DevBuf<double> align_part;
 };
 
 // A context with an open border reduce refuses new mass until the reduce is committed or aborted
@@ -343,41 +411,18 @@ static int fail(tsdf_ctx* c, int code, const char* fmt, ...) {
             return fail((c), TSDF_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_));      \
     } while (0)
 
-// Pair slots per ray: the distinct bricks a DDA over the band can visit.  A segment of length L
-// (voxels) covers at most E = floor(L) + 2 cells along an axis, E cells cross at most
-// floor((E - 1) / 8) + 1 brick boundaries, and a line crosses them monotonically, one axis per
-// step: 1 + 3 * crossings bricks.  (5 cm / 15 cm: 4.)  Exceeding it is reported (OVF_PAIRS).
-static uint32_t pairs_per_ray(const tsdf_params& p) {
-    double band;  // band length in voxels along the ray
-    if (p.space_carving) band = (p.max_range + p.sdf_trunc) / p.voxel_size;
-    else band = 2.0 * p.sdf_trunc / p.voxel_size;
-    const double e = std::floor(band) + 2.0;
-    const double crossings = std::floor((e - 1.0) / TSDF_BRICK_SIDE) + 1.0;
-    return (uint32_t)(1.0 + 3.0 * crossings);
-}
-
-// Sample slots per ray: a ray's gated voxels are among its DDA voxels, at most
-// 1 + 3 (floor(band) + 2) (5 cm / 15 cm: 25).
-static uint32_t samples_per_ray(const tsdf_params& p) {
-    double band;
-    if (p.space_carving) band = (p.max_range + p.sdf_trunc) / p.voxel_size;
-    else band = 2.0 * p.sdf_trunc / p.voxel_size;
-    return (uint32_t)(1.0 + 3.0 * (std::floor(band) + 2.0));
-}
-
-// Launch one batch (desc offsets relative to d_xyz); fills the workgroup prefix of D.
 static int check_and_replay(tsdf_ctx* c);
 static int drain_all(tsdf_ctx* c);
 static int emit_metrics(tsdf_ctx* c);
 
-// Before launch seq rewrites its host ring slot: launch seq - RING (the slot's previous user) must
-// have read it (its k_upload raised the progress word to seq - RING + 1).  Waits like an event
+// Before launch seq rewrites its host ring slot: launch seq - N (the slot's previous user) must
+// have read it (its k_upload raised the progress word to seq - N + 1).  Waits like an event
 // synchronize (spin, then yield), and checks the batch streams for errors while it waits.
 static int ring_wait(tsdf_ctx* c, uint64_t seq) {
-    if (seq < (uint64_t)tsdf_ctx::RING) return TSDF_OK;
-    const unsigned long long need = seq - tsdf_ctx::RING + 1;
+    if (seq < (uint64_t)ScanRing::N) return TSDF_OK;
+    const unsigned long long need = seq - ScanRing::N + 1;
     for (uint64_t i = 0;; i++) {
-        if (__atomic_load_n(c->h_ring_done, __ATOMIC_ACQUIRE) >= need) return TSDF_OK;
+        if (__atomic_load_n(c->ring.done.p, __ATOMIC_ACQUIRE) >= need) return TSDF_OK;
         if (i < 64) continue;
         std::this_thread::yield();
         if ((i & 1023) == 0) {
@@ -387,79 +432,86 @@ static int ring_wait(tsdf_ctx* c, uint64_t seq) {
                 if (e == hipErrorNotReady) idle = false;
                 else if (e != hipSuccess) HIPCHK(c, e);
             }
-            if (idle && __atomic_load_n(c->h_ring_done, __ATOMIC_ACQUIRE) < need)
+            if (idle && __atomic_load_n(c->ring.done.p, __ATOMIC_ACQUIRE) < need)
                 return fail(c, TSDF_EHIP, "scan-record ring: upload %llu never completed",
                             (unsigned long long)(need - 1));
         }
     }
 }
 
+// ---- launch: one batch through the pipeline ---------------------------------------
+
+// Cross-batch order.  Batch b runs on stream bst[b & 1] (serial: every batch on bst[0], where
+// stream order is the whole rule) and orders itself against batch b - 1 on the other stream with
+// two events of b - 1: `compact` (ev_compact: its table `touched` words are consumed, so b's front
+// end may mark bricks) and `end` (ev_integ: its k_finish ran, so b may fuse into the same bricks).
+//
+//   pipeline    wait before front | before back | before integrate   ev_compact of b recorded
+//   0 serial           -          |      -      |        -           never
+//   1 overlap       compact       |      -      |       end          after k_compact
+//   2 lean          compact       |     end     |        -           after the back end
+//
+// 1: b's front end runs beside b - 1's back end and integrate.  2: only b's front end and compact
+// overlap b - 1's integrate; the back end always runs alone, and b + 1's front end starts after it.
+// The waits and records in launch() carry the row numbers they belong to.
+
+// Launch one batch (desc offsets relative to d_xyz); fills the workgroup prefix of D.
 static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
     if (D.n_scans == 0) return TSDF_OK;
     c->ht.start();
-    if (c->metrics && !c->in_replay && c->batch_id - c->metrics_next >= METRIC_RING - 8) {
-        int rc = drain_all(c);  // the device ring of batch records would wrap
-        if (!rc) rc = check_and_replay(c);
-        if (!rc) rc = emit_metrics(c);
-        if (rc) return rc;
-    }
-    if (c->can_grow && !c->in_replay && c->log.size() >= 1024) {
-        // device-pointer batches stay replayable until a check: bound the log
+    // -- checkpoints: the device ring of batch records would wrap (metrics), or the replay log
+    // grows without bound (device-pointer batches stay replayable until a check)
+    const bool ring_full = c->metrics && c->batch_id - c->metrics_next >= METRIC_RING - 8;
+    if (!c->in_replay && (ring_full || (c->can_grow && c->log.size() >= 1024))) {
         int rc = drain_all(c);
         if (!rc) rc = check_and_replay(c);
+        if (!rc && ring_full) rc = emit_metrics(c);
         if (rc) return rc;
     }
+    // -- block prefix: RPB rays per workgroup, one scan per workgroup
     D.s[0].blk = 0;
     for (uint32_t s = 0; s < D.n_scans; s++)
         D.s[s + 1].blk = D.s[s].blk + (D.s[s + 1].off - D.s[s].off + RPB - 1) / RPB;
     D.n_blocks = D.s[D.n_scans].blk;
-    if (D.n_blocks > c->max_blocks)
-        return fail(c, TSDF_EINVAL, "batch needs %u workgroups > %u", D.n_blocks, c->max_blocks);
+    if (D.n_blocks > c->plan.max_blocks)
+        return fail(c, TSDF_EINVAL, "batch needs %u workgroups > %u", D.n_blocks, c->plan.max_blocks);
     const int par = (int)(c->batch_id & 1);
-    c->ht.lap(0);
-#ifndef TSDF_TWO_STREAM_SERIAL
+    c->ht.lap(HT_PRE);
     // serial batches share one stream (stream order replaces the cross-stream waits); pipelined
     // batches alternate between two
-    const bool cross = c->p.pipeline != 0;
-#else
-    const bool cross = true;
-#endif
+    const bool cross = c->p.pipeline != 0, lean = c->p.pipeline == 2;
     hipStream_t st = c->bst[cross ? par : 0];
     Table T = c->T;
-    T.cell = c->cell2[par];
+    T.cell = c->K.cell[par];
     const Work& W = c->W2[par];
+    const bool prev = cross && c->batch_id > 0;  // a previous batch on the other stream
     EventTimer* tm = c->timer;
     if (tm) tm->cur_batch = c->batch_id;
     if (c->metrics) c->metrics_info.push_back({c->batch_id, D.n_scans, D.s[D.n_scans].off});
-    // staging uploads, imports, ... (an idle context stream has nothing to order against)
+    // -- waits: staging uploads, imports, ... (an idle context stream has nothing to order against)
     if (hipStreamQuery(c->stream) != hipSuccess) {
         HIPCHK(c, hipEventRecord(c->ev_main, c->stream));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_main, 0));
     }
-    if (c->batch_id > 0 && cross)  // pipelined: after the previous batch's compact; else after all of it
-        HIPCHK(c, hipStreamWaitEvent(st, c->p.pipeline ? c->ev_compact[par ^ 1]
-                                                       : c->ev_integ[par ^ 1], 0));
-    c->ht.lap(1);
-    // the batch's scan records -> the device (a ring slot; the host slot is reused once its copy ran)
-    const uint64_t seq = c->ring_next++;
-    const int slot = (int)(seq % tsdf_ctx::RING);
-    {
-        int rc = ring_wait(c, seq);
-        if (rc) return rc;
-    }
-    c->ht.lap(8);
-    ScanRec* hs = c->h_ring + (size_t)slot * (MAX_BATCH + 1);
-    ScanRec* ds = c->d_ring + (size_t)slot * (MAX_BATCH + 1);
-    std::memcpy(hs, D.s, (D.n_scans + 1) * sizeof(ScanRec));
-    c->ht.lap(9);
-    HIPCHK(c, launch_upload(c->d_ring_src + (size_t)slot * (MAX_BATCH + 1), ds,
-                            (uint32_t)((D.n_scans + 1) * sizeof(ScanRec)), c->d_ring_done, seq + 1,
-                            st));
-    c->ht.lap(10);
-    c->ht.lap(2);
+    if (prev) HIPCHK(c, hipStreamWaitEvent(st, c->ev_compact[par ^ 1], 0));  // before front: 1, 2
+    c->ht.lap(HT_WAITS);
+    // -- ring upload: the batch's scan records -> the device (a ring slot; the host slot is reused
+    // once its copy ran)
+    ScanRing& ring = c->ring;
+    const uint64_t seq = ring.next++;
+    const int slot = (int)(seq % ScanRing::N);
+    if (const int rc = ring_wait(c, seq)) return rc;
+    c->ht.lap(HT_RING_WAIT);
+    const size_t at = (size_t)slot * (MAX_BATCH + 1);
+    ScanRec* ds = ring.dev + at;
+    std::memcpy(ring.host + at, D.s, (D.n_scans + 1) * sizeof(ScanRec));
+    c->ht.lap(HT_RING_COPY);
+    HIPCHK(c, launch_upload(ring.host_dev + at, ds, (uint32_t)((D.n_scans + 1) * sizeof(ScanRec)),
+                            ring.done_dev, seq + 1, st));
+    c->ht.lap(HT_UPLOAD);
     const BatchRef B{D.n_scans, D.n_blocks, ds};
-    // MergedTsdfIntegrator: the batch's points bundled per (scan, voxel) first; the walk kernels
-    // then read one ray per bundle, in the slot of its first point (tsdf_merged.hip)
+    // -- pre-pass (MergedTsdfIntegrator): the batch's points bundled per (scan, voxel) first; the
+    // walk kernels then read one ray per bundle, in the slot of its first point (tsdf_merged.hip)
     RayConst R = c->R;
     const float* d_rays = d_xyz;
     if (c->merged && D.n_blocks) {
@@ -468,46 +520,44 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
         d_rays = c->mg[par].xyz_out;
         R.ray_w = c->mg[par].w_out;
     }
-    // a small batch (a live node's 1-8 scans) fuses wave-per-brick, in table order (no k_order)
-    const bool small = !c->fused && D.n_scans <= (uint32_t)c->small_ns;
-    const int k_front = c->fused ? KIND_WALK : KIND_COUNT;
-    const int k_back = c->fused ? KIND_SPANS : KIND_PLACE;
+    // -- front end and compact.  A small batch (a live node's 1-8 scans) fuses wave-per-brick, in
+    // table order (no k_order)
+    const bool small = !c->plan.fused && D.n_scans <= (uint32_t)c->small_ns;
+    const int k_front = c->plan.fused ? KIND_WALK : KIND_COUNT;
+    const int k_back = c->plan.fused ? KIND_SPANS : KIND_PLACE;
     // per-kernel times: the two-walk kernels record their own dispatch timestamps (KTime, no
     // marker packets); the single walk's stages are bracketed by marker events
-    auto kt = [&](int kind) { return tm && !c->fused && tm->want(kind) ? tm->timing(kind) : KTime{}; };
+    auto kt = [&](int kind) { return tm && !c->plan.fused && tm->want(kind) ? tm->timing(kind) : KTime{}; };
     if (D.n_blocks) {
-        if (tm && c->fused) tm->begin(k_front, st);
+        if (tm && c->plan.fused) tm->begin(k_front, st);
         if (c->R.sec_on) HIPCHK(c, launch_sector_flags(d_rays, B, R, W, c->G, par, st));
-        if (c->fused) HIPCHK(c, launch_walk(d_rays, B, R, T, W, c->G, par, c->nstep, st));
+        if (c->plan.fused) HIPCHK(c, launch_walk(d_rays, B, R, T, W, c->G, par, c->plan.nstep, st));
         else HIPCHK(c, launch_count(d_rays, B, R, T, W, c->G, par, st, kt(KIND_COUNT),
                                     !c->R.sec_on && D.n_blocks <= c->count_wide,
                                     !c->R.sec_on && c->count_paired));
-        c->ht.lap(3);
-        if (tm && c->fused) tm->next(k_front, KIND_COMPACT, st);
-        HIPCHK(c, launch_compact(B, T, W, c->G, par, c->fused, st, kt(KIND_COMPACT)));
-        c->ht.lap(4);
+        c->ht.lap(HT_FRONT);
+        if (tm && c->plan.fused) tm->next(k_front, KIND_COMPACT, st);
+        HIPCHK(c, launch_compact(B, T, W, c->G, par, c->plan.fused, st, kt(KIND_COMPACT)));
+        c->ht.lap(HT_COMPACT);
 #if defined(TSDF_SEPARATE_ORDER) && !defined(TSDF_NO_ORDER)
         if (!small) HIPCHK(c, launch_order(W, c->G, par, st));
 #endif
     }
-    // pipeline 1: batch b+1's front end waits for this batch's compact (it may run beside this
-    // batch's place and integrate); pipeline 2: for its place, and this batch's place waits for
-    // batch b-1's end, so only k_count / k_compact of b+1 overlap k_integrate of b and k_place
-    // always runs alone
-    const bool lean = c->p.pipeline == 2;
-    if (cross && c->p.pipeline && !lean) HIPCHK(c, hipEventRecord(c->ev_compact[par], st));
-    if (lean && c->batch_id > 0) HIPCHK(c, hipStreamWaitEvent(st, c->ev_integ[par ^ 1], 0));
+    if (cross && !lean) HIPCHK(c, hipEventRecord(c->ev_compact[par], st));  // after compact: 1
+    // -- back end
+    if (prev && lean) HIPCHK(c, hipStreamWaitEvent(st, c->ev_integ[par ^ 1], 0));  // before back: 2
     if (D.n_blocks) {
-        if (tm && c->fused) tm->next(KIND_COMPACT, k_back, st);
-        if (c->fused) HIPCHK(c, launch_spans(B, c->R, T, W, c->G, par, c->nstep, st));
+        if (tm && c->plan.fused) tm->next(KIND_COMPACT, k_back, st);
+        if (c->plan.fused) HIPCHK(c, launch_spans(B, c->R, T, W, c->G, par, c->plan.nstep, st));
         else HIPCHK(c, launch_place(d_rays, B, R, T, W, c->G, par, st, kt(KIND_PLACE)));
-        c->ht.lap(5);
-        if (tm && c->fused) tm->end(k_back, st);
+        c->ht.lap(HT_BACK);
+        if (tm && c->plan.fused) tm->end(k_back, st);
     }
-    if (lean) HIPCHK(c, hipEventRecord(c->ev_compact[par], st));  // batch b+1's front-end wait
-    if (c->batch_id > 0 && cross && !lean) HIPCHK(c, hipStreamWaitEvent(st, c->ev_integ[par ^ 1], 0));
+    if (lean) HIPCHK(c, hipEventRecord(c->ev_compact[par], st));  // after back: 2
+    // -- integrate
+    if (prev && !lean) HIPCHK(c, hipStreamWaitEvent(st, c->ev_integ[par ^ 1], 0));  // before integrate: 1
     if (D.n_blocks) {
-        if (tm && c->fused) tm->begin(KIND_INTEGRATE, st);
+        if (tm && c->plan.fused) tm->begin(KIND_INTEGRATE, st);
         if (small) {
             HIPCHK(c, launch_integrate_small(B, c->R, T, W, c->Pl, c->G, par, st, kt(KIND_INTEGRATE)));
         } else {
@@ -517,16 +567,17 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
 #else
             const Work& Wi = W;
 #endif
-            HIPCHK(c, launch_integrate(B, c->R, T, Wi, c->Pl, c->G, par, c->fused, c->max_batch > 64, st,
+            HIPCHK(c, launch_integrate(B, c->R, T, Wi, c->Pl, c->G, par, c->plan.fused, c->max_batch > 64, st,
                                        kt(KIND_INTEGRATE)));
         }
-        if (tm && c->fused) tm->end(KIND_INTEGRATE, st);
-        c->ht.lap(6);
+        if (tm && c->plan.fused) tm->end(KIND_INTEGRATE, st);
+        c->ht.lap(HT_INTEGRATE);
     }
+    // -- finish and the host's books
     HIPCHK(c, launch_finish(c->G, par, (uint32_t)c->batch_id, st));
-    if (cross) {  // pipelined: the other stream's next batches wait on this batch's end
-        HIPCHK(c, hipEventRecord(c->ring_ev[slot], st));
-        c->ev_integ[par] = c->ring_ev[slot];
+    if (cross) {  // the batch's end: the other stream's next batches wait on it
+        HIPCHK(c, hipEventRecord(ring.ev[slot], st));
+        c->ev_integ[par] = ring.ev[slot];
     }
     if (c->can_grow) c->log.push_back({c->batch_id, d_xyz, D});
     for (int k = 0; k < 2; k++)  // a host batch: its staging buffer's last reader
@@ -534,7 +585,7 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
             c->stage_reader[k] = c->batch_id;
             HIPCHK(c, hipEventRecord(c->stage_ev[k], st));
         }
-    c->ht.lap(7);
+    c->ht.lap(HT_FINISH);
     c->ht.n++;
     c->batch_id++;
     c->n_batches++;
@@ -550,13 +601,11 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
 // The context stream waits for every launched batch (read-outs, imports, sync).
 static int join(tsdf_ctx* c) {
     if (c->batch_id == 0) return TSDF_OK;
-#ifndef TSDF_TWO_STREAM_SERIAL
     if (!c->p.pipeline) {  // serial batches: one stream, no per-batch marker; one now
         HIPCHK(c, hipEventRecord(c->ev_main, c->bst[0]));
         HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_main, 0));
         return TSDF_OK;
     }
-#endif
     for (int q = 0; q < 2; q++)
         if (c->batch_id > (uint64_t)q) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_integ[q], 0));
     return TSDF_OK;
@@ -574,7 +623,7 @@ static int fan_copy_range(tsdf_ctx* c, tsdf_ctx* s, float* dst, const float* src
     HIPCHK(c, c->device == s->device
                   ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream)
                   : hipMemcpyPeerAsync(dst, c->device, src, s->device, bytes, c->stream));
-    if (!c->bc_ev) HIPCHK(c, hipEventCreateWithFlags(&c->bc_ev, hipEventDisableTiming));
+    if (!c->bc_ev) HIPCHK(c, c->bc_ev.create());
     HIPCHK(c, hipEventRecord(c->bc_ev, c->stream));
     HIPCHK(s, hipSetDevice(s->device));
     HIPCHK(s, hipStreamWaitEvent(s->stream, c->bc_ev, 0));
@@ -617,52 +666,28 @@ static int settle(tsdf_ctx* c) {
 
 // ---- capacity: brick pool, hash table and per-brick work lists -----------------
 
-struct Capacity {
-    uint64_t max_bricks = 0, cap = 0;
-    uint32_t max_active = 0;
-    uint64_t* keys = nullptr;
-    uint32_t* slots = nullptr;
-    uint32_t* touched = nullptr;
-    uint64_t* brick_keys = nullptr;
-    float* sdf = nullptr;
-    float* weight = nullptr;
-    uint32_t* cell[2] = {nullptr, nullptr};
-    uint4* active[2] = {nullptr, nullptr};
-    uint4* active_ord[2] = {nullptr, nullptr};
-    uint4* cagg[2] = {nullptr, nullptr};
-
-    void free_all() {
-        void* d[] = {keys, slots, touched, brick_keys, sdf, weight, cell[0], cell[1], active[0],
-                     active[1], active_ord[0], active_ord[1], cagg[0], cagg[1]};
-        for (void* q : d)
-            if (q) (void)hipFree(q);
-        *this = Capacity{};
-    }
-};
-
 // Allocate (and clear: empty table, zero cells) the capacity-dependent buffers for max_bricks bricks;
-// the pool's contents are the caller's.  Allocation failure is TSDF_ENOMEM with nothing leaked.
+// the pool's contents are the caller's.  Allocation failure is TSDF_ENOMEM; K frees what it got.
 static int alloc_capacity(tsdf_ctx* c, uint64_t max_bricks, Capacity& K) {
     K = Capacity{};
     K.max_bricks = max_bricks;
     K.cap = next_pow2(2 * max_bricks);
-    K.max_active = (uint32_t)std::min<uint64_t>(K.cap, c->slots);
-    const size_t cells = K.cap * c->T.cell_stride * (c->fused ? sizeof(uint64_t) : sizeof(uint32_t));
-    hipError_t e = hipMalloc(&K.keys, K.cap * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&K.slots, K.cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&K.touched, K.cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMalloc(&K.brick_keys, max_bricks * sizeof(uint64_t));
-    if (e == hipSuccess) e = hipMalloc(&K.sdf, max_bricks * BRICK_VOX * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&K.weight, max_bricks * BRICK_VOX * sizeof(float));
+    K.max_active = (uint32_t)std::min<uint64_t>(K.cap, c->plan.slots);
+    const size_t cells = K.cap * c->plan.cell_stride * (c->plan.fused ? sizeof(uint64_t) : sizeof(uint32_t));
+    hipError_t e = K.keys.alloc(K.cap);
+    if (e == hipSuccess) e = K.slots.alloc(K.cap);
+    if (e == hipSuccess) e = K.touched.alloc(K.cap);
+    if (e == hipSuccess) e = K.brick_keys.alloc(max_bricks);
+    if (e == hipSuccess) e = K.sdf.alloc(max_bricks * BRICK_VOX);
+    if (e == hipSuccess) e = K.weight.alloc(max_bricks * BRICK_VOX);
     for (int q = 0; q < 2 && e == hipSuccess; q++) {
-        e = hipMalloc(&K.cell[q], cells);
-        if (e == hipSuccess) e = hipMalloc(&K.active[q], (size_t)K.max_active * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc(&K.active_ord[q], (size_t)K.max_active * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc(&K.cagg[q], compact_chunks(K.cap) * 2 * sizeof(uint4));
+        e = K.cell[q].alloc_bytes(cells);
+        if (e == hipSuccess) e = K.active[q].alloc(K.max_active);
+        if (e == hipSuccess) e = K.active_ord[q].alloc(K.max_active);
+        if (e == hipSuccess) e = K.cagg[q].alloc(compact_chunks(K.cap) * 2);
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        K.free_all();
         return fail(c, TSDF_ENOMEM, "device allocation for %llu bricks failed",
                     (unsigned long long)max_bricks);
     }
@@ -670,41 +695,42 @@ static int alloc_capacity(tsdf_ctx* c, uint64_t max_bricks, Capacity& K) {
     if (e == hipSuccess) e = launch_fill_u32(K.slots, UNASSIGNED, K.cap, c->stream);
     if (e == hipSuccess) e = hipMemsetAsync(K.touched, 0, K.cap * sizeof(uint32_t), c->stream);
     for (int q = 0; q < 2 && e == hipSuccess; q++) e = hipMemsetAsync(K.cell[q], 0, cells, c->stream);
-    if (e != hipSuccess) {
-        K.free_all();
-        return fail(c, TSDF_EHIP, "capacity init: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(c, TSDF_EHIP, "capacity init: %s", hipGetErrorString(e));
     return TSDF_OK;
 }
 
-// Make K the context's capacity (the previous buffers are freed; K is emptied).
-static void install_capacity(tsdf_ctx* c, Capacity& K) {
-    Capacity old;
-    old.keys = c->T.keys; old.slots = c->T.slots; old.touched = c->T.touched;
-    old.brick_keys = c->T.brick_keys; old.sdf = c->Pl.sdf; old.weight = c->Pl.weight;
+// The kernels' argument structs, filled from the owners (c->K, c->lane): after create, after a
+// new capacity is installed and after a list grew.  T.cell is the parity-0 cells; launch() passes
+// a Table with its parity's.
+static void set_views(tsdf_ctx* c) {
+    const Capacity& K = c->K;
+    c->T = Table{K.keys, K.slots, K.touched, K.cell[0], K.brick_keys, K.cap - 1,
+                 (uint32_t)K.max_bricks, c->plan.cell_stride};
+    c->Pl = Pool{K.sdf, K.weight};
+    const uint64_t mg_cap = c->merged ? c->plan.batch_points : 0;
     for (int q = 0; q < 2; q++) {
-        old.cell[q] = c->cell2[q];
-        old.active[q] = c->W2[q].active;
-        old.active_ord[q] = c->W2[q].active_ord;
-        old.cagg[q] = c->W2[q].cagg;
+        const Lane& L = c->lane[q];
+        c->W2[q] = Work{L.pair, L.blk, L.blk_n, L.plan, L.fb, L.smp, K.active[q], K.active_ord[q],
+                        L.ord_hist, K.cagg[q], L.act, L.rsv, L.rsv_n, L.spn, c->plan.maxp,
+                        K.max_active, c->max_fb, c->max_smp, c->max_spn};
+        c->mg[q] = MgBufs{L.mg_xyz, L.mg_w, mg_cap, L.mg_ekey, L.mg_eidx, L.mg_bcnt, L.mg_bst,
+                          L.mg_bscan, mg_cap ? mg_buckets_max(mg_cap) : 0};
     }
-    old.free_all();
-    c->cap = K.cap;
-    c->T.keys = K.keys; c->T.slots = K.slots; c->T.touched = K.touched;
-    c->T.brick_keys = K.brick_keys;
-    c->T.mask = K.cap - 1;
-    c->T.max_bricks = (uint32_t)K.max_bricks;
-    c->T.cell = K.cell[0];
-    c->Pl.sdf = K.sdf; c->Pl.weight = K.weight;
-    c->Wk.max_active = K.max_active;
-    for (int q = 0; q < 2; q++) {
-        c->cell2[q] = K.cell[q];
-        c->W2[q].active = K.active[q];
-        c->W2[q].active_ord = K.active_ord[q];
-        c->W2[q].cagg = K.cagg[q];
-        c->W2[q].max_active = K.max_active;
-    }
-    K = Capacity{};
+}
+
+// ---- the host's protocol with Globals (tsdf_device.h) --------------------------------------------
+
+// The check word: Globals' first five fields, read in one copy; the clears span adjacent fields,
+// and the reset after a grow (everything before tot_vox) takes the check word and both counters
+struct GlobalsCheck { uint32_t pool_count, overflow, failed, retry, fail_id; };
+static_assert(offsetof(Globals, pool_count) == 0 && offsetof(Globals, overflow) == 4 &&
+              offsetof(Globals, failed) == 8 && offsetof(Globals, retry) == 12 &&
+              offsetof(Globals, fail_id) == 16 && offsetof(Globals, ctr) < offsetof(Globals, tot_vox),
+              "the host reads and clears Globals' head by these offsets");
+// Zero `words` adjacent u32 fields from `first` on
+static hipError_t globals_clear(uint32_t* first, int words) {
+    const uint32_t z[2] = {0u, 0u};
+    return hipMemcpy(first, z, 4 * words, hipMemcpyHostToDevice);
 }
 
 // Grow the pool (and table, cells, lists) to hold at least `need` bricks: x2 or more, capped by
@@ -720,7 +746,7 @@ static int grow_capacity(tsdf_ctx* c, uint64_t need) {
     uint32_t pc = 0;
     HIPCHK(c, hipMemcpy(&pc, &c->G->pool_count, 4, hipMemcpyDeviceToHost));
     const uint64_t valid = std::min<uint64_t>(pc, old);
-    Capacity K;
+    Capacity K;  // (freed with this scope if it is not installed)
     int rc = alloc_capacity(c, nb, K);
     if (rc) return rc;
     hipError_t e = hipSuccess;
@@ -737,17 +763,14 @@ static int grow_capacity(tsdf_ctx* c, uint64_t need) {
     if (e == hipSuccess)
         e = hipMemsetAsync(K.weight + valid * BRICK_VOX, 0, (nb - valid) * BRICK_VOX * 4, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);  // the old pool is read before the free
-    if (e != hipSuccess) {
-        K.free_all();
-        return fail(c, TSDF_EHIP, "grow: %s", hipGetErrorString(e));
-    }
-    install_capacity(c, K);
+    if (e != hipSuccess) return fail(c, TSDF_EHIP, "grow: %s", hipGetErrorString(e));
+    c->K = std::move(K);  // installed: the old buffers are freed
+    set_views(c);
     HIPCHK(c, launch_rehash(c->T, (uint32_t)valid, c->G, c->stream));
-    // the failed batches' counters and flags go; the pool keeps its valid bricks
-    const uint32_t pcv = (uint32_t)valid;
+    // the failed batches' counters and flags go; the pool keeps its valid bricks; retry stays on
+    const uint32_t pcv = (uint32_t)valid, retry = 1u;
     HIPCHK(c, hipMemsetAsync(c->G, 0, offsetof(Globals, tot_vox), c->stream));
     HIPCHK(c, hipMemcpyAsync(&c->G->pool_count, &pcv, 4, hipMemcpyHostToDevice, c->stream));
-    const uint32_t retry = 1u;
     HIPCHK(c, hipMemcpyAsync(&c->G->retry, &retry, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->n_grows++;
@@ -757,46 +780,22 @@ static int grow_capacity(tsdf_ctx* c, uint64_t need) {
 // Double one of the work lists in both batch parities, up to `limit` entries of `bytes` each.
 // `counted`: the growth shows in tsdf_get_stats' n_grows (the fallback pairs' never has).
 template <class T>
-static int grow_list(tsdf_ctx* c, T* Work::*list, uint32_t Work::*max, uint64_t limit, size_t bytes,
-                     const char* what, bool counted) {
-    const uint64_t n = std::min<uint64_t>(2ull * (c->Wk.*max), limit);
-    if (n <= c->Wk.*max) return fail(c, TSDF_ENOMEM, "%s at its limit", what);
-    T* f[2] = {nullptr, nullptr};
-    hipError_t e = hipMalloc(&f[0], n * bytes);
-    if (e == hipSuccess) e = hipMalloc(&f[1], n * bytes);
+static int grow_list(tsdf_ctx* c, DevBuf<T> Lane::*list, uint32_t tsdf_ctx::*max, uint64_t limit,
+                     size_t bytes, const char* what, bool counted) {
+    const uint64_t n = std::min<uint64_t>(2ull * (c->*max), limit);
+    if (n <= c->*max) return fail(c, TSDF_ENOMEM, "%s at its limit", what);
+    DevBuf<T> f[2];
+    hipError_t e = f[0].alloc_bytes(n * bytes);
+    if (e == hipSuccess) e = f[1].alloc_bytes(n * bytes);
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        for (auto q : f) if (q) (void)hipFree(q);
         return fail(c, TSDF_ENOMEM, "%s allocation failed", what);
     }
-    for (int q = 0; q < 2; q++) {
-        (void)hipFree(c->W2[q].*list);
-        c->W2[q].*list = f[q];
-        c->W2[q].*max = (uint32_t)n;
-    }
-    c->Wk.*max = (uint32_t)n;
+    for (int q = 0; q < 2; q++) c->lane[q].*list = std::move(f[q]);  // frees the old list
+    c->*max = (uint32_t)n;
+    set_views(c);
     if (counted) c->n_grows++;
     return TSDF_OK;
-}
-
-// The fallback-pair lists (OVF_FB), up to the 26-bit index space.
-static int grow_fb(tsdf_ctx* c) {
-    return grow_list(c, &Work::fb, &Work::max_fb, 1ull << 26, sizeof(uint4), "fallback pair list",
-                     false);
-}
-
-// The sample lists (OVF_SMP), up to the 32-bit sample index (single walk: the workgroup regions,
-// up to the span record's 30-bit sample position).
-static uint64_t smp_limit(const tsdf_ctx* c) { return c->fused ? (1ull << 30) : 0xFFFFFFF0ull; }
-static int grow_smp(tsdf_ctx* c) {
-    return grow_list(c, &Work::smp, &Work::max_smp, smp_limit(c), smp_bytes(c->R.sem), "sample list",
-                     true);
-}
-
-// The span lists (OVF_SPN, single walk).
-static int grow_spn(tsdf_ctx* c) {
-    return grow_list(c, &Work::spn, &Work::max_spn, 0xFFFFFFF0ull, sizeof(uint32_t), "span list",
-                     true);
 }
 
 // Every launched batch complete: the context stream waits for them and drains.
@@ -813,15 +812,14 @@ static int drain_all(tsdf_ctx* c) {
 // reports the overflow.
 static int check_and_replay(tsdf_ctx* c) {
     for (int round = 0; round < 64; round++) {
-        struct { uint32_t pool_count, overflow, failed, retry, fail_id; } g;
+        GlobalsCheck g;
         HIPCHK(c, hipMemcpy(&g, c->G, sizeof g, hipMemcpyDeviceToHost));
         if (!g.failed) {
             c->log.clear();
             return TSDF_OK;
         }
         if (!c->can_grow) {  // committed anyway (G->retry = 0): the overflow stays for tsdf_sync
-            const uint32_t z[2] = {0u, 0u};
-            HIPCHK(c, hipMemcpy(&c->G->failed, z, 4, hipMemcpyHostToDevice));
+            HIPCHK(c, globals_clear(&c->G->failed, 1));
             c->log.clear();
             return TSDF_OK;
         }
@@ -832,9 +830,18 @@ static int check_and_replay(tsdf_ctx* c) {
             rc = TSDF_OK;
             if (g.overflow & (OVF_TABLE | OVF_POOL | OVF_ACTIVE))
                 rc = grow_capacity(c, std::max<uint64_t>(g.pool_count, c->T.max_bricks + 1));
-            if (rc == TSDF_OK && (g.overflow & OVF_FB)) rc = grow_fb(c);
-            if (rc == TSDF_OK && (g.overflow & OVF_SMP)) rc = grow_smp(c);
-            if (rc == TSDF_OK && (g.overflow & OVF_SPN)) rc = grow_spn(c);
+            // fallback pairs: up to the 26-bit index space (never counted in n_grows); samples: up
+            // to the 32-bit sample index (single walk: the span record's 30-bit sample position)
+            if (rc == TSDF_OK && (g.overflow & OVF_FB))
+                rc = grow_list(c, &Lane::fb, &tsdf_ctx::max_fb, 1ull << 26, sizeof(uint4),
+                               "fallback pair list", false);
+            if (rc == TSDF_OK && (g.overflow & OVF_SMP))
+                rc = grow_list(c, &Lane::smp, &tsdf_ctx::max_smp,
+                               c->plan.fused ? (1ull << 30) : 0xFFFFFFF0ull, smp_bytes(c->R.sem),
+                               "sample list", true);
+            if (rc == TSDF_OK && (g.overflow & OVF_SPN))
+                rc = grow_list(c, &Lane::spn, &tsdf_ctx::max_spn, 0xFFFFFFF0ull, sizeof(uint32_t),
+                               "span list", true);
             if (rc == TSDF_EHIP) return rc;
         }
         // the replay: from the first failed batch on, in order
@@ -845,11 +852,9 @@ static int check_and_replay(tsdf_ctx* c) {
         c->log.clear();
         if (rc != TSDF_OK) {  // cannot grow: commit what fits from now on
             c->can_grow = false;
-            const uint32_t z[2] = {0u, 0u};  // failed, retry
-            HIPCHK(c, hipMemcpy(&c->G->failed, z, 8, hipMemcpyHostToDevice));
+            HIPCHK(c, globals_clear(&c->G->failed, 2));  // failed, retry
         } else {  // grown: the replay re-raises whatever still does not fit
-            const uint32_t z[2] = {0u, 0u};  // overflow, failed
-            HIPCHK(c, hipMemcpy(&c->G->overflow, z, 8, hipMemcpyHostToDevice));
+            HIPCHK(c, globals_clear(&c->G->overflow, 2));  // overflow, failed
         }
         c->in_replay = true;
         for (auto& L : rep) {
@@ -906,7 +911,7 @@ static int emit_metrics(tsdf_ctx* c) {
         if (ms) {
             double path = 0;
             for (int k = 0; k < KIND_N; k++) path += (*ms)[k];
-            if (c->fused)
+            if (c->plan.fused)
                 fprintf(c->metrics,
                         ", \"kernel_ms\": {\"walk\": %.5f, \"compact\": %.5f, \"spans\": %.5f, "
                         "\"integrate\": %.5f}",
@@ -1068,6 +1073,8 @@ int tsdf_abi_version(void) { return TSDF_ABI_VERSION; }
 
 const char* tsdf_last_error(const tsdf_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
+// In order: the fan-out links go, the pending work settles, the streams drain, and the context's
+// owners free what they hold (a half-built context's empty owners free nothing).
 void tsdf_destroy(tsdf_ctx* c) {
     if (!c) return;
     // fan-out links (tsdf_integrate_sectors): a leader hands its followers their pending points
@@ -1092,49 +1099,45 @@ void tsdf_destroy(tsdf_ctx* c) {
         }
     }
     if (c->metrics) fclose(c->metrics);
-    if (c->brd_sent) (void)hipFree(c->brd_sent);
-    if (c->align_part) (void)hipFree(c->align_part);
-    for (auto& b : c->brd_backup) (void)hipFree(b.first);
     delete c->timer;
     delete c->pack;
-    void* dev[] = {c->T.keys,        c->T.slots,
-                   c->T.touched,
-                   c->T.brick_keys,  c->Pl.sdf,          c->Pl.weight,     c->G,
-                   c->cell2[0],      c->cell2[1],        c->stage2[0],     c->stage2[1],
-                   c->W2[0].pair,    c->W2[0].blk,       c->W2[0].blk_n, c->W2[0].fb,
-                   c->W2[0].smp,     c->W2[0].active,  c->W2[0].active_ord, c->W2[1].active_ord,
-                   c->W2[0].ord_hist, c->W2[1].ord_hist,    c->W2[1].pair,    c->W2[1].blk,
-                   c->W2[1].blk_n, c->W2[1].fb,        c->W2[1].smp,     c->W2[1].active,
-                   c->W2[0].cagg,    c->W2[1].cagg,      c->W2[0].act,     c->W2[1].act,
-                   c->W2[0].spn,     c->W2[1].spn,
-                   c->W2[0].plan,    c->W2[1].plan,      c->W2[0].rsv,     c->W2[1].rsv,
-                   c->W2[0].rsv_n,   c->W2[1].rsv_n};
-    for (void* d : dev)
-        if (d) (void)hipFree(d);
-    for (int i = 0; i < 2; i++) {
-        if (c->h_stage[i]) (void)hipHostFree(c->h_stage[i]);
-        if (c->stage_done[i]) (void)hipEventDestroy(c->stage_done[i]);
-        MgBufs& M = c->mg[i];
-        for (void* q : {(void*)M.xyz_out, (void*)M.w_out, (void*)M.ekey, (void*)M.eidx,
-                        (void*)M.bcnt, (void*)M.bst, (void*)M.bscan})
-            if (q) (void)hipFree(q);
-    }
-    if (c->bc_ev) (void)hipEventDestroy(c->bc_ev);
-    for (int q = 0; q < 2; q++) {
-        if (c->bst[q]) (void)hipStreamDestroy(c->bst[q]);
-        if (c->ev_compact[q]) (void)hipEventDestroy(c->ev_compact[q]);
-        if (c->stage_ev[q]) (void)hipEventDestroy(c->stage_ev[q]);
-    }
-    if (c->ev_main) (void)hipEventDestroy(c->ev_main);
-    for (int k = 0; k < tsdf_ctx::RING; k++)
-        if (c->ring_ev[k]) (void)hipEventDestroy(c->ring_ev[k]);
-    if (c->h_ring) (void)hipHostFree(c->h_ring);
-    if (c->h_ring_done) (void)hipHostFree(c->h_ring_done);
-    if (c->d_ring) (void)hipFree(c->d_ring);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;  // the owners free what they hold
 }
 
+// The ray model's constants, derived from the params
+static RayConst ray_const(const tsdf_params& p, int band_vox) {
+    RayConst R{};
+    R.vs = (float)p.voxel_size;
+    R.inv_vs = 1.0f / R.vs;
+    R.tau = (float)p.sdf_trunc;
+    R.min_range = (float)p.min_range;
+    R.max_range = (float)p.max_range;
+    R.carving = p.space_carving ? 1 : 0;
+    R.tau2_lo = (float)(((double)R.tau * (1.0 - 0x1p-20)) * ((double)R.tau * (1.0 - 0x1p-20)));
+    R.tau2_hi = (float)(((double)R.tau * (1.0 + 0x1p-20)) * ((double)R.tau * (1.0 + 0x1p-20)));
+    // internal sem 3: Voxblox with per-sample weights (the 1/z^2 weight, stored by k_place; the
+    // merged integrator's bundles, which carry summed weights)
+    R.depth_w = p.semantics == TSDF_SEM_VOXBLOX && p.depth_weight ? 1 : 0;
+    R.sem = plan_sem(p);
+    // (ray_w stays null: set per launch to the pre-pass output, merged)
+    R.allow_clear = p.allow_clear ? 1 : 0;
+    R.dropoff = p.use_weight_dropoff ? 1 : 0;
+    R.max_weight = p.max_weight;
+    R.w0_cap = p.max_weight > 0.0f && p.max_weight < TSDF_W0_CAP ? p.max_weight : TSDF_W0_CAP;
+    R.bg = p.semantics == TSDF_SEM_VOXBLOX ? 0.0f : R.tau;
+    R.tau_m_vs = R.tau - R.vs;
+    // TSDF_SECTOR_RULE_INDEX: the context takes an index share; the kernels' azimuth filter is off
+    if (!(p.n_sectors > 1 && p.sector_rule == TSDF_SECTOR_RULE_INDEX))
+        sector_bounds(p.sector_yaw0, p.sector, p.n_sectors, R);
+    const double vs_d = (double)R.vs;  // VDBVolume keeps voxel_size as float
+    R.hvs_d = vs_d * 0.5;              // exact
+    R.inv_s_d = 1.0 / vs_d;
+    R.gate_d2 = gate_threshold(R.tau);
+    R.band_vox = band_vox;
+    return R;
+}
+
+// Three steps: the ray constants, the sizing plan (ctx_plan.h), the allocations.
 static int create_impl(tsdf_ctx* c, const tsdf_params* p) {
     c->p = *p;
     int ndev = 0;
@@ -1144,229 +1147,97 @@ static int create_impl(tsdf_ctx* c, const tsdf_params* p) {
         return fail(c, TSDF_EINVAL, "device_id %d out of range (%d devices)", p->device_id, ndev);
     c->device = p->device_id;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPCHK(c, c->stream.create());
     for (int q = 0; q < 2; q++) {
-        HIPCHK(c, hipStreamCreateWithFlags(&c->bst[q], hipStreamNonBlocking));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_compact[q], hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->stage_ev[q], hipEventDisableTiming));
+        HIPCHK(c, c->bst[q].create());
+        HIPCHK(c, c->ev_compact[q].create());
+        HIPCHK(c, c->stage_ev[q].create());
     }
-    HIPCHK(c, hipEventCreateWithFlags(&c->ev_main, hipEventDisableTiming));
+    HIPCHK(c, c->ev_main.create());
 
-    c->R.vs = (float)p->voxel_size;
-    c->R.inv_vs = 1.0f / c->R.vs;
-    c->R.tau = (float)p->sdf_trunc;
-    c->R.min_range = (float)p->min_range;
-    c->R.max_range = (float)p->max_range;
-    c->R.carving = p->space_carving ? 1 : 0;
-    c->R.tau2_lo = (float)(((double)c->R.tau * (1.0 - 0x1p-20)) * ((double)c->R.tau * (1.0 - 0x1p-20)));
-    c->R.tau2_hi = (float)(((double)c->R.tau * (1.0 + 0x1p-20)) * ((double)c->R.tau * (1.0 + 0x1p-20)));
-    // internal sem 3: Voxblox with the 1/z^2 weight (per-sample weights stored by k_place)
-    c->R.depth_w = p->semantics == TSDF_SEM_VOXBLOX && p->depth_weight ? 1 : 0;
-    // MergedTsdfIntegrator: bundles carry summed weights, so per-sample weights too (sem 3)
-    c->merged = p->semantics == TSDF_SEM_VOXBLOX && p->voxblox_method == TSDF_VB_MERGED;
-    c->R.sem = c->R.depth_w || c->merged ? 3 : p->semantics;
-    c->R.ray_w = nullptr;  // set per launch to the pre-pass output (merged)
-    c->R.allow_clear = p->allow_clear ? 1 : 0;
-    c->R.dropoff = p->use_weight_dropoff ? 1 : 0;
-    c->R.max_weight = p->max_weight;
-    c->R.w0_cap = p->max_weight > 0.0f && p->max_weight < TSDF_W0_CAP ? p->max_weight : TSDF_W0_CAP;
-    c->R.bg = p->semantics == TSDF_SEM_VOXBLOX ? 0.0f : c->R.tau;
-    c->R.tau_m_vs = c->R.tau - c->R.vs;
+    c->plan = ctx_plan(*p, PlanConsts{RPB, MAX_BATCH, WLK_THREADS, SPAN, VOX_LIMIT});
+    if (!c->plan.refusal.empty()) return fail(c, TSDF_EINVAL, "%s", c->plan.refusal.c_str());
+    c->R = ray_const(*p, c->plan.band_vox);
+    c->merged = plan_merged(*p);
     c->idx_rule = p->n_sectors > 1 && p->sector_rule == TSDF_SECTOR_RULE_INDEX;
-    if (c->idx_rule) c->R.sec_on = 0;
-    else sector_bounds(p->sector_yaw0, p->sector, p->n_sectors, c->R);
-    const double vs_d = (double)c->R.vs;  // VDBVolume keeps voxel_size as float
-    c->R.hvs_d = vs_d * 0.5;               // exact
-    c->R.inv_s_d = 1.0 / vs_d;
-    c->R.gate_d2 = gate_threshold(c->R.tau);
-    {
-        const double band = p->space_carving ? (p->max_range + p->sdf_trunc) / p->voxel_size
-                                             : 2.0 * p->sdf_trunc / p->voxel_size;
-        c->R.band_vox = (int)std::min(std::ceil(band) + 4.0, (double)(VOX_LIMIT / 2));
-    }
-
-    // Points one batch may hold: max_batch full scans, unless the per-ray worst cases (pair slots,
-    // sample slots — large with space carving) exceed the u32 index space or the sample budget;
-    // the host queue then cuts batches by points.  A single scan must always fit.
-    const uint32_t maxp = pairs_per_ray(*p);
-    const uint32_t spr = samples_per_ray(*p);
-    // sample list: the worst case (spr per ray) of the rays a context keeps — 1 / n_sectors of them
-    // when sharded — capped at 2^30 samples (8 GiB); an overflow grows it (OVF_SMP)
-    const uint64_t smp_budget = 1ull << 30;
-    c->max_batch = p->max_batch;
-    uint64_t bp = p->max_points * c->max_batch;
-    bp = std::min<uint64_t>(bp, 0xFFFFFFF0ull / maxp);
-    if (p->max_pairs) bp = std::min<uint64_t>(bp, p->max_pairs / maxp);  // caller-imposed cap
-    if (bp < p->max_points)
-        return fail(c, TSDF_EINVAL,
-                    "max_points %llu exceeds what one batch can hold (%llu: %u pair and %u sample "
-                    "slots per ray)", (unsigned long long)p->max_points, (unsigned long long)bp,
-                    maxp, spr);
-    // Single walk: k_walk keeps a ray's samples in one register slot per DDA step, so
-    // the band's walk must have a proven bound: a segment of L voxels crosses at most floor(L |u_a|)
-    // + 1 boundaries per axis, i.e. visits <= sqrt(3) L + 4 voxels.  Carving and Voxblox clearing
-    // rays (length up to max_range) keep the two-walk path, the default (tsdf_params.walk).
-    {
-        const double band = 2.0 * p->sdf_trunc / p->voxel_size;
-        const double steps = std::floor(std::sqrt(3.0) * band * (1.0 + 1e-4)) + 5.0;
-        const bool clearing = p->semantics == TSDF_SEM_VOXBLOX && p->allow_clear &&
-                              std::isfinite(p->max_range);
-        c->fused = p->walk == TSDF_WALK_SINGLE && !p->space_carving && !clearing && maxp <= 4 &&
-                   c->R.sem != 3 &&
-                   steps <= 32.0;
-        c->nstep = steps <= 16.0 ? 16 : 32;
-    }
-    const uint64_t stg = (uint64_t)WLK_THREADS * (uint64_t)c->nstep;  // samples per k_walk region
-    if (c->fused) {
-        // the span record addresses 2^30 samples: at most 2^30 / stg k_walk workgroups per batch
-        const uint64_t lim = ((1ull << 30) / (2 * stg) - MAX_BATCH - 1) * RPB;
-        bp = std::min<uint64_t>(bp, lim);
-        if (bp < p->max_points)
-            return fail(c, TSDF_EINVAL, "max_points %llu exceeds a single-walk batch (%llu)",
-                        (unsigned long long)p->max_points, (unsigned long long)bp);
-    }
     c->max_points = p->max_points;
-    c->batch_points = bp;
-    const uint64_t slots = bp * maxp;
-    c->slots = slots;
-    c->max_blocks = (uint32_t)(c->batch_points / RPB + MAX_BATCH + 1);
-    const uint32_t nsec = std::max<uint32_t>(1u, p->n_sectors);
-    if (c->fused) {
-        // 64-bit cells and a totals cell after the last scan; the pair and fallback lists are not
-        // used; one region of stg samples per k_walk workgroup (sharded: this GPU's share of the
-        // blocks, grown on OVF_SMP); span records ~ samples / SPAN + one partial span per run
-        c->T.cell_stride = (c->max_batch + 2u) & ~1u;
-        c->Wk.maxp = maxp;
-        const uint64_t reg_blocks = nsec > 1 ? std::min<uint64_t>(
-            c->max_blocks, c->max_blocks * 5ull / (4ull * nsec) + 2ull * c->max_batch + 64) : c->max_blocks;
-        c->Wk.max_smp = (uint32_t)std::min<uint64_t>(2 * reg_blocks * stg, 1ull << 30);
-        c->Wk.max_spn = (uint32_t)std::min<uint64_t>(
-            bp * spr / SPAN / nsec + 2 * reg_blocks * 256, 0xFFFFFFF0ull);
-        c->Wk.max_fb = 4;
-    } else {
-        c->T.cell_stride = (c->max_batch + 3u) & ~3u;
-        c->Wk.maxp = maxp;
-        c->Wk.max_smp = (uint32_t)std::min<uint64_t>(
-            std::min<uint64_t>(bp * spr / nsec, smp_budget), 0xFFFFFFF0ull);
-        // fallback pairs (a workgroup's LDS brick hash is full): rare without carving, the rule with
-        // it (the fallback index has 26 bits; past it pairs are dropped and OVF_FB reported)
-        c->Wk.max_fb = (uint32_t)std::min<uint64_t>(
-            p->space_carving ? slots : std::max<uint64_t>(slots / 16, 1u << 20), 1u << 26);
-        c->Wk.max_spn = 4;
-    }
+    c->max_batch = p->max_batch;
+    c->max_fb = c->plan.max_fb;
+    c->max_smp = c->plan.max_smp;
+    c->max_spn = c->plan.max_spn;
 
     for (int q = 0; q < 2; q++) {  // one set per batch parity (capacity-independent part)
-        Work& W = c->W2[q];
-        W = c->Wk;
-        HIPCHK(c, hipMalloc(&W.pair, (c->fused ? 4 : slots) * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc(&W.blk, (size_t)c->max_blocks * 2 * HCAP * sizeof(uint4)));
-        HIPCHK(c, hipMalloc(&W.blk_n, (size_t)c->max_blocks * 2 * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc(&W.plan, (size_t)c->max_blocks * 2 * PLAN_STRIDE * sizeof(uint32_t)));
+        Lane& L = c->lane[q];
+        HIPCHK(c, L.pair.alloc(c->plan.fused ? 4 : c->plan.slots));
+        HIPCHK(c, L.blk.alloc((size_t)c->plan.max_blocks * 2 * HCAP));
+        HIPCHK(c, L.blk_n.alloc((size_t)c->plan.max_blocks * 2));
+        HIPCHK(c, L.plan.alloc((size_t)c->plan.max_blocks * 2 * PLAN_STRIDE));
 #ifdef TSDF_CNT_SPLIT
-        HIPCHK(c, hipMalloc(&W.rsv, (size_t)c->max_blocks * HCAP * sizeof(uint4)));
-        HIPCHK(c, hipMalloc(&W.rsv_n, (size_t)c->max_blocks * sizeof(uint32_t)));
+        HIPCHK(c, L.rsv.alloc((size_t)c->plan.max_blocks * HCAP));
+        HIPCHK(c, L.rsv_n.alloc(c->plan.max_blocks));
 #endif
-        HIPCHK(c, hipMalloc(&W.fb, (size_t)W.max_fb * sizeof(uint4)));
-        HIPCHK(c, hipMalloc(&W.smp, (size_t)W.max_smp * smp_bytes(c->R.sem)));
-        HIPCHK(c, hipMalloc(&W.spn, (size_t)W.max_spn * sizeof(uint32_t)));
+        HIPCHK(c, L.fb.alloc(c->max_fb));
+        HIPCHK(c, L.smp.alloc_bytes((size_t)c->max_smp * smp_bytes(c->R.sem)));
+        HIPCHK(c, L.spn.alloc(c->max_spn));
         // (slice, size class) histogram, then first positions (k_compact; zero between batches)
-        HIPCHK(c, hipMalloc(&W.ord_hist, 2 * 64 * 32 * sizeof(uint32_t)));
-        HIPCHK(c, hipMemset(W.ord_hist, 0, 2 * 64 * 32 * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc(&W.act, (size_t)c->max_blocks * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc(&c->stage2[q], c->batch_points * 3 * sizeof(float)));
+        HIPCHK(c, L.ord_hist.alloc(2 * 64 * 32));
+        HIPCHK(c, hipMemset(L.ord_hist, 0, 2 * 64 * 32 * sizeof(uint32_t)));
+        HIPCHK(c, L.act.alloc(c->plan.max_blocks));
+        HIPCHK(c, c->stage2[q].alloc(c->plan.batch_points * 3));
         if (c->merged) {  // the bundling pre-pass: one set per parity, batch_points entries
-            MgBufs& M = c->mg[q];
-            const uint64_t n = c->batch_points;
-            M.cap = n;
-            M.nb_cap = mg_buckets_max(n);
-            HIPCHK(c, hipMalloc(&M.ekey, n * 8));
-            HIPCHK(c, hipMalloc(&M.eidx, n * 4));
-            HIPCHK(c, hipMalloc(&M.bcnt, (size_t)4 * MG_REPLICAS * M.nb_cap));
-            HIPCHK(c, hipMemset(M.bcnt, 0, (size_t)4 * MG_REPLICAS * M.nb_cap));  // zero between batches
-            HIPCHK(c, hipMalloc(&M.bst, (size_t)4 * (M.nb_cap + 1)));
-            HIPCHK(c, hipMalloc(&M.bscan, (size_t)4 * M.nb_cap));
-            HIPCHK(c, hipMalloc(&M.xyz_out, n * 12));
-            HIPCHK(c, hipMalloc(&M.w_out, n * 4));
+            const uint64_t n = c->plan.batch_points, nb = mg_buckets_max(n);
+            HIPCHK(c, L.mg_ekey.alloc(n));
+            HIPCHK(c, L.mg_eidx.alloc(n));
+            HIPCHK(c, L.mg_bcnt.alloc(MG_REPLICAS * nb));
+            HIPCHK(c, hipMemset(L.mg_bcnt, 0, 4 * MG_REPLICAS * nb));  // zero between batches
+            HIPCHK(c, L.mg_bst.alloc(nb + 1));
+            HIPCHK(c, L.mg_bscan.alloc(nb));
+            HIPCHK(c, L.mg_xyz.alloc(n * 3));
+            HIPCHK(c, L.mg_w.alloc(n));
         }
     }
-    HIPCHK(c, hipMalloc(&c->G, sizeof(Globals)));
+    HIPCHK(c, c->G.alloc(1));
     if (const char* e = std::getenv("TSDF_SMALL_NS")) c->small_ns = std::max(0, std::min(8, std::atoi(e)));
     if (const char* e = std::getenv("TSDF_COUNT_WIDE")) c->count_wide = (uint32_t)std::max(0, std::atoi(e));
     if (const char* e = std::getenv("TSDF_COUNT_PAIRED")) c->count_paired = std::atoi(e) != 0;
-    {
-        // host staging threads: 3 workers + the caller (TSDF_PACK_THREADS overrides; 1 = none)
-        int nt = 4;
-        if (const char* e = std::getenv("TSDF_PACK_THREADS")) nt = std::max(1, std::atoi(e));
-        nt = std::min<int>(nt, (int)std::max(1u, std::thread::hardware_concurrency()));
-        if (nt > 1) {
-            try {
-                c->pack = new PackPool(nt - 1);
-            } catch (...) {  // no threads: the caller's thread stages alone
-                c->pack = nullptr;
-            }
+    // host staging threads: 3 workers + the caller (TSDF_PACK_THREADS overrides; 1 = none)
+    int nt = 4;
+    if (const char* e = std::getenv("TSDF_PACK_THREADS")) nt = std::max(1, std::atoi(e));
+    nt = std::min<int>(nt, (int)std::max(1u, std::thread::hardware_concurrency()));
+    if (nt > 1) {
+        try {
+            c->pack = new PackPool(nt - 1);
+        } catch (...) {  // no threads: the caller's thread stages alone
+            c->pack = nullptr;
         }
     }
-    HIPCHK(c, hipHostMalloc(&c->h_ring, tsdf_ctx::RING * (MAX_BATCH + 1) * sizeof(ScanRec),
-                            hipHostMallocDefault));
-    HIPCHK(c, hipMalloc(&c->d_ring, tsdf_ctx::RING * (MAX_BATCH + 1) * sizeof(ScanRec)));
-    {
-        void* dp = nullptr;
-        HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_ring, 0));
-        c->d_ring_src = static_cast<const ScanRec*>(dp);
-        HIPCHK(c, hipHostMalloc(&c->h_ring_done, 64, hipHostMallocDefault));
-        *c->h_ring_done = 0;
-        HIPCHK(c, hipHostGetDevicePointer(&dp, c->h_ring_done, 0));
-        c->d_ring_done = static_cast<unsigned long long*>(dp);
-    }
-    for (int k = 0; k < tsdf_ctx::RING; k++)
-        HIPCHK(c, hipEventCreateWithFlags(&c->ring_ev[k], hipEventDisableTiming));
+    HIPCHK(c, c->ring.create());
     HIPCHK(c, hipMemsetAsync(c->G, 0, sizeof(Globals), c->stream));
     // the brick pool, hash table and per-brick work lists (grown later by grow_capacity)
-    {
-        Capacity K;
-        const int rc = alloc_capacity(c, p->max_bricks, K);
-        if (rc) return rc;
-        HIPCHK(c, launch_fill(K.sdf, c->R.bg, p->max_bricks * BRICK_VOX, c->stream));
-        HIPCHK(c, hipMemsetAsync(K.weight, 0, p->max_bricks * BRICK_VOX * sizeof(float), c->stream));
-        install_capacity(c, K);
-    }
-    c->T.cell = c->cell2[0];
+    Capacity K;
+    if (const int rc = alloc_capacity(c, p->max_bricks, K)) return rc;
+    HIPCHK(c, launch_fill(K.sdf, c->R.bg, p->max_bricks * BRICK_VOX, c->stream));
+    HIPCHK(c, hipMemsetAsync(K.weight, 0, p->max_bricks * BRICK_VOX * sizeof(float), c->stream));
+    c->K = std::move(K);  // installed
+    set_views(c);
     for (int i = 0; i < 2; i++) {
-        HIPCHK(c, hipHostMalloc(&c->h_stage[i], c->max_points * 3 * sizeof(float),
-                                hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&c->stage_done[i], hipEventDisableTiming));
+        HIPCHK(c, c->h_stage[i].alloc(c->max_points * 3));
+        HIPCHK(c, c->stage_done[i].create());
     }
     c->can_grow = p->max_bricks_hard == 0 || p->max_bricks_hard > p->max_bricks;
-    {
-        const uint32_t retry = c->can_grow ? 1u : 0u;
-        HIPCHK(c, hipMemcpyAsync(&c->G->retry, &retry, 4, hipMemcpyHostToDevice, c->stream));
-    }
+    const uint32_t retry = c->can_grow ? 1u : 0u;
+    HIPCHK(c, hipMemcpyAsync(&c->G->retry, &retry, 4, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    {
-        static uint8_t all[TSDF_MC_TABLES][256][32];
-        for (int t = 0; t < TSDF_MC_TABLES; t++) std::memcpy(all[t], mc_table(t).tab, sizeof all[t]);
-        HIPCHK(c, upload_mc_table(all, mc_table().edge));
-    }
+    static uint8_t all[TSDF_MC_TABLES][256][32];
+    for (int t = 0; t < TSDF_MC_TABLES; t++) std::memcpy(all[t], mc_table(t).tab, sizeof all[t]);
+    HIPCHK(c, upload_mc_table(all, mc_table().edge));
     return TSDF_OK;
 }
 
 int tsdf_create(const tsdf_params* p, tsdf_ctx** out) {
     if (!p || !out) return TSDF_EINVAL;
     *out = nullptr;
-    if (!(p->voxel_size > 0) || !(p->sdf_trunc > 0) || p->brick_side != TSDF_BRICK_SIDE ||
-        p->weight_mode != TSDF_WEIGHT_CONSTANT || p->max_bricks == 0 ||
-        p->max_bricks >= 0xFFFFFFF0ull || p->max_points == 0 || !(p->min_range >= 0) ||
-        !(p->max_range > p->min_range) || p->max_batch == 0 || p->max_batch > TSDF_MAX_BATCH ||
-        (p->semantics != TSDF_SEM_VDBFUSION && p->semantics != TSDF_SEM_VOXBLOX &&
-         p->semantics != TSDF_SEM_VDBFUSION_F64) ||
-        (p->semantics == TSDF_SEM_VOXBLOX && !(p->max_weight > 0.0f)) ||
-        (p->voxblox_method != TSDF_VB_SIMPLE && p->voxblox_method != TSDF_VB_MERGED) ||
-        p->sector_input < TSDF_SECTOR_INPUT_FANOUT || p->sector_input > TSDF_SECTOR_INPUT_SPLIT ||
-        (p->sector_rule != TSDF_SECTOR_RULE_WORLD && p->sector_rule != TSDF_SECTOR_RULE_INDEX) ||
-        (p->n_sectors > 1 && p->sector >= p->n_sectors) || !std::isfinite(p->sector_yaw0) ||
-        (p->max_bricks_hard && p->max_bricks_hard < p->max_bricks))
-        return TSDF_EINVAL;
-    if (p->space_carving && !std::isfinite(p->max_range)) return TSDF_EINVAL;
+    if (!params_valid(*p)) return TSDF_EINVAL;
     tsdf_ctx* c = new (std::nothrow) tsdf_ctx();
     if (!c) return TSDF_ENOMEM;
     const int rc = create_impl(c, p);
@@ -1472,7 +1343,7 @@ static int pend_push(tsdf_ctx* c, uint64_t n, const ScanPose& P) {
 
 // Room for a scan of n points in the pending batch (flushing it first if needed).
 static int pend_room(tsdf_ctx* c, uint64_t n) {
-    if (c->pend.n_scans == c->max_batch || c->pend.s[c->pend.n_scans].off + n > c->batch_points)
+    if (c->pend.n_scans == c->max_batch || c->pend.s[c->pend.n_scans].off + n > c->plan.batch_points)
         return flush(c);
     return TSDF_OK;
 }
@@ -1657,7 +1528,7 @@ static int broadcast_follower(tsdf_ctx* c, tsdf_ctx* c0, float* buf0, uint64_t o
         // H2D: this context's own PCIe copy of hx; the leader must not reuse hx first
         HIPCHK(c, hipMemcpyAsync(c->stage2[c->pend_stage] + 3 * off, hx, n * 12,
                                  hipMemcpyHostToDevice, c->stream));
-        if (!c->bc_ev) HIPCHK(c, hipEventCreateWithFlags(&c->bc_ev, hipEventDisableTiming));
+        if (!c->bc_ev) HIPCHK(c, c->bc_ev.create());
         HIPCHK(c, hipEventRecord(c->bc_ev, c->stream));
         HIPCHK(c, hipStreamWaitEvent(c0->stream, c->bc_ev, 0));  // (reported by c: see mirror)
     }
@@ -1679,7 +1550,7 @@ static int sectors_broadcast(tsdf_ctx* const* ctxs, uint32_t n_ctx, const Record
     const uint64_t off0 = c0->pend.s[c0->pend.n_scans].off;
     float* buf0 = c0->stage2[c0->pend_stage];
     if (n) HIPCHK(c0, hipMemcpyAsync(buf0 + 3 * off0, hx, n * 12, hipMemcpyHostToDevice, c0->stream));
-    if (!c0->bc_ev) HIPCHK(c0, hipEventCreateWithFlags(&c0->bc_ev, hipEventDisableTiming));
+    if (!c0->bc_ev) HIPCHK(c0, c0->bc_ev.create());
     HIPCHK(c0, hipEventRecord(c0->bc_ev, c0->stream));
     for (uint32_t k = 1; k < n_ctx; k++)
         if (const int rc = mirror(ctxs, k, broadcast_follower(ctxs[k], c0, buf0, off0, hx, n, P, fanout)))
@@ -1932,7 +1803,7 @@ static int batch_device_impl(tsdf_ctx* c, const float* d_xyz, const uint64_t* of
         while (s < n_scans && D.n_scans < c->max_batch) {
             idx_share(c, offs[s + 1] - offs[s], lo, hi);
             const uint64_t x0 = offs[s] + lo - b0, nb = D.s[D.n_scans].off + (hi - lo);
-            if (nb > c->batch_points || x0 + (hi - lo) > 0xFFFFFFFFull) break;
+            if (nb > c->plan.batch_points || x0 + (hi - lo) > 0xFFFFFFFFull) break;
             const double* q = origins + (uint64_t)pose_stride * s;
             set_pose(D, D.n_scans, pose_stride == 7 ? pose_of(q) : pose_of_origin(q));
             D.s[D.n_scans].xoff = (uint32_t)(x0 - D.s[D.n_scans].off);
@@ -2199,7 +2070,7 @@ int tsdf_align_terms_device(tsdf_ctx* c, const float* d_xyz, uint64_t n, const d
     rc = drain(c);
     if (rc) return rc;
     constexpr size_t words = ((size_t)ALIGN_MAX_WG + 1) * ALIGN_PART;
-    if (!c->align_part) HIPCHK(c, hipMalloc(&c->align_part, words * sizeof(double)));
+    if (!c->align_part) HIPCHK(c, c->align_part.alloc(words));
     const OsPose P = os_pose(pose);
     HIPCHK(c, launch_align(c->T, c->Pl, c->R, d_xyz, n, P, min_weight, c->align_part, c->stream));
     double r[29];  // H's upper triangle row-major, b, sum r^2, the valid count
@@ -2768,7 +2639,7 @@ static int border_pack_impl(tsdf_ctx* c, const uint64_t* d_all_keys, const uint6
     HIPCHK(c, launch_border_pack(c->T, c->Pl, c->R.bg, (uint32_t)nb, rank, d_owner, d_aux + MAX_WORLD,
                                  d_rows, (uint32_t)rows, d_send, /*reset=*/false, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->brd_sent = tmp.take(d_rows);
+    c->brd_sent.reset(tmp.take(d_rows));
     c->brd_n_sent = rows;
     return TSDF_OK;
 }
@@ -2819,7 +2690,7 @@ int tsdf_border_merge_device(tsdf_ctx* c, const uint32_t* d_recv, const uint64_t
     // the backup joins the abort's restore list only once its snapshot is launched (a
     // failed launch left uninitialised rows for the restore to write over held bricks)
     HIPCHK(c, launch_border_snapshot(c->T, c->Pl, d_recv, total, bk, c->stream));
-    c->brd_backup.push_back({tmp.take(bk), total});
+    c->brd_backup.emplace_back(DevBuf<uint32_t>(tmp.take(bk)), total);
     uint64_t row = 0;
     for (uint32_t r = 0; r < world; r++) {  // sources in ascending rank order
         if (recv_counts[r])
@@ -2851,10 +2722,8 @@ int tsdf_border_commit_device(tsdf_ctx* c, int32_t commit) {
     if (e != hipSuccess)  // the transaction stays open: the caller may retry
         return fail(c, TSDF_EHIP, "border %s: %s", commit ? "commit" : "abort",
                     hipGetErrorString(e));
-    if (c->brd_sent) (void)hipFree(c->brd_sent);
-    c->brd_sent = nullptr;
+    c->brd_sent.reset();
     c->brd_n_sent = 0;
-    for (auto& b : c->brd_backup) (void)hipFree(b.first);
     c->brd_backup.clear();
     c->brd_open = false;
     return TSDF_OK;
