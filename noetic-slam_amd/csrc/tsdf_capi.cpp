@@ -243,8 +243,8 @@ struct Capacity {
 // for fb / smp / spn, doubled on overflow (grow_list), and the merged pre-pass' set (MgBufs;
 // Voxblox MergedTsdfIntegrator only, tsdf_merged.hip)
 struct Lane {
-    DevBuf<uint32_t> pair, blk_n, plan, spn, ord_hist, act, rsv_n;  // (rsv, rsv_n: TSDF_CNT_SPLIT)
-    DevBuf<uint4> blk, fb, rsv;
+    DevBuf<uint32_t> pair, blk_n, plan, spn, ord_hist, act;
+    DevBuf<uint4> blk, fb;
     DevBuf<uint2> smp;
     DevBuf<uint64_t> mg_ekey;
     DevBuf<uint32_t> mg_eidx, mg_bcnt, mg_bst, mg_bscan;
@@ -521,7 +521,7 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
         R.ray_w = c->mg[par].w_out;
     }
     // -- front end and compact.  A small batch (a live node's 1-8 scans) fuses wave-per-brick, in
-    // table order (no k_order)
+    // table order (not k_compact's size order)
     const bool small = !c->plan.fused && D.n_scans <= (uint32_t)c->small_ns;
     const int k_front = c->plan.fused ? KIND_WALK : KIND_COUNT;
     const int k_back = c->plan.fused ? KIND_SPANS : KIND_PLACE;
@@ -539,9 +539,6 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
         if (tm && c->plan.fused) tm->next(k_front, KIND_COMPACT, st);
         HIPCHK(c, launch_compact(B, T, W, c->G, par, c->plan.fused, st, kt(KIND_COMPACT)));
         c->ht.lap(HT_COMPACT);
-#if defined(TSDF_SEPARATE_ORDER) && !defined(TSDF_NO_ORDER)
-        if (!small) HIPCHK(c, launch_order(W, c->G, par, st));
-#endif
     }
     if (cross && !lean) HIPCHK(c, hipEventRecord(c->ev_compact[par], st));  // after compact: 1
     // -- back end
@@ -561,12 +558,8 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
         if (small) {
             HIPCHK(c, launch_integrate_small(B, c->R, T, W, c->Pl, c->G, par, st, kt(KIND_INTEGRATE)));
         } else {
-#ifndef TSDF_NO_ORDER
             Work Wi = W;
             Wi.active = W.active_ord;  // largest bricks first (k_compact's size order)
-#else
-            const Work& Wi = W;
-#endif
             HIPCHK(c, launch_integrate(B, c->R, T, Wi, c->Pl, c->G, par, c->plan.fused, c->max_batch > 64, st,
                                        kt(KIND_INTEGRATE)));
         }
@@ -711,7 +704,7 @@ static void set_views(tsdf_ctx* c) {
     for (int q = 0; q < 2; q++) {
         const Lane& L = c->lane[q];
         c->W2[q] = Work{L.pair, L.blk, L.blk_n, L.plan, L.fb, L.smp, K.active[q], K.active_ord[q],
-                        L.ord_hist, K.cagg[q], L.act, L.rsv, L.rsv_n, L.spn, c->plan.maxp,
+                        L.ord_hist, K.cagg[q], L.act, L.spn, c->plan.maxp,
                         K.max_active, c->max_fb, c->max_smp, c->max_spn};
         c->mg[q] = MgBufs{L.mg_xyz, L.mg_w, mg_cap, L.mg_ekey, L.mg_eidx, L.mg_bcnt, L.mg_bst,
                           L.mg_bscan, mg_cap ? mg_buckets_max(mg_cap) : 0};
@@ -1172,10 +1165,6 @@ static int create_impl(tsdf_ctx* c, const tsdf_params* p) {
         HIPCHK(c, L.blk.alloc((size_t)c->plan.max_blocks * 2 * HCAP));
         HIPCHK(c, L.blk_n.alloc((size_t)c->plan.max_blocks * 2));
         HIPCHK(c, L.plan.alloc((size_t)c->plan.max_blocks * 2 * PLAN_STRIDE));
-#ifdef TSDF_CNT_SPLIT
-        HIPCHK(c, L.rsv.alloc((size_t)c->plan.max_blocks * HCAP));
-        HIPCHK(c, L.rsv_n.alloc(c->plan.max_blocks));
-#endif
         HIPCHK(c, L.fb.alloc(c->max_fb));
         HIPCHK(c, L.smp.alloc_bytes((size_t)c->max_smp * smp_bytes(c->R.sem)));
         HIPCHK(c, L.spn.alloc(c->max_spn));

@@ -212,12 +212,10 @@ struct Work {
     uint2* smp;  // x = truncated sdf (f32 bits), y = scan << 9 | local voxel; Voxblox 1/z^2 (sem 3):
                  // 12-B records (x, y, weight f32 bits), smp_store / smp_load
     uint4* active;  // (h, slot, toff, cnt) per active brick (k_compact)
-    uint4* active_ord;  // the same records, largest size class first (k_order; k_integrate's list)
+    uint4* active_ord;  // the same records, largest size class first (k_compact; k_integrate's list)
     uint32_t* ord_hist; // per (slice, size class): counts [64][32], then first positions [64][32]
     uint4* cagg;    // k_compact: per table chunk (touched bricks, samples, new bricks), then bases
     uint32_t* act;  // sector sharding: the k_count blocks holding a ray of this GPU's sector (n_act)
-    uint4* rsv;     // TSDF_CNT_SPLIT variant: per k_count block, its distinct bricks for k_resolve
-    uint32_t* rsv_n;  // (key, n0 | n1 << 16, run-list index 0 | index 1 << 11 | scan << 22); count
     uint32_t* spn;  // single walk: span records (sample position | (samples - 1) << 30), per brick
                     // contiguous and scan-ordered (k_spans)
     uint32_t maxp;        // pair slots per ray
@@ -352,8 +350,6 @@ hipError_t launch_upload(const void* host_src, void* dst, uint32_t bytes,
                          unsigned long long* done, unsigned long long seq, hipStream_t st);
 // capacity growth: re-insert pool slots [0, n) of the new table from brick_keys
 hipError_t launch_rehash(const Table& T, uint32_t n, Globals* G, hipStream_t st);
-// Orders the batch's active bricks by size class, largest first (k_integrate's load balance).
-hipError_t launch_order(const Work& Wk, Globals* G, int parity, hipStream_t st);
 // fused: samples through the span list (single walk); big: batches of more than 64 scans
 // k_integrate_small: batches of at most a few scans, one wave per brick (tsdf_integrate.hip)
 hipError_t launch_integrate_small(const BatchRef& D, const RayConst& R, const Table& T,

@@ -39,32 +39,8 @@ constexpr uint32_t INT_CAP = INT_PER * INT_THREADS;  // samples (>= live cells) 
 #endif
 // LDS: 12 B per cell + ~9.5 KB per workgroup; residency as LDS allows
 constexpr int INT_BLOCKS_PER_CU = (160 * 1024) / (INT_CAP * 12 + 10 * 1024);
-#ifndef TSDF_INT_WIN
-#define TSDF_INT_WIN 64
-#endif
-#if TSDF_INT_WIN == 64
 typedef unsigned long long MaskT;  // a voxel's scans in the window, one bit per scan
-#define MASK_POPC(m) __popcll(m)
-#else
-typedef uint32_t MaskT;
-#define MASK_POPC(m) __popc(m)
-#endif
-// LDS position of brick voxel l = (z * 8 + y) * 8 + x in k_integrate's per-voxel arrays.  A/B knob
-// (round 6): TSDF_INT_SKEW=1 skews each z layer by one element, so voxels of one (x, y) column (64
-// elements apart: one bank) fall in different banks -- measured slower (k_integrate 0.399 vs 0.377
-// ms headline, 1.18 vs 1.07 ms C4: the index arithmetic costs more than the conflicts it removes)
-// A/B knob (round 6): TSDF_INT_ZERO_IN_FUSE=1 zeroes the live cells in the fuse chains that
-// consumed them instead of in a pass before each window's accumulation -- measured slower
-// (k_integrate 0.385 vs 0.375 ms headline, 1.085 vs 1.065 ms C4: the stores lengthen the chains)
-#ifndef TSDF_INT_ZERO_IN_FUSE
-#define TSDF_INT_ZERO_IN_FUSE 0
-#endif
-#ifndef TSDF_INT_SKEW
-#define TSDF_INT_SKEW 0
-#endif
-#define VOXL(l) ((l) + TSDF_INT_SKEW * ((l) >> 6))
-constexpr int BRICK_VOX_LDS = BRICK_VOX + TSDF_INT_SKEW * (BRICK_VOX / 64);
-constexpr uint32_t INT_MAX_WIN = TSDF_INT_WIN;       // scans per window (mask bits)
+constexpr uint32_t INT_MAX_WIN = 64;                 // scans per window (mask bits)
 // single walk (FUSED): the register cache holds INT_SPT span records' samples per thread, so a
 // chunk is INT_SCH spans; a window also keeps its spans <= INT_SCH (one chunk per window)
 #ifndef TSDF_INT_SPT
@@ -117,9 +93,9 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
     __shared__ unsigned long long cA[CAP];  // live cell: sum of trunc(s w * 2^32)
     __shared__ CellB cB[CAP];               // live cell: sample count / sum of trunc(w 2^32)
     const float tau = R.tau;
-    __shared__ MaskT sMask[BRICK_VOX_LDS];     // voxel: scans (bit t - t0) observed in the window
-    __shared__ uint32_t sBase[BRICK_VOX_LDS];  // voxel: first live cell
-    __shared__ float sS[BRICK_VOX_LDS], sW[BRICK_VOX_LDS];
+    __shared__ MaskT sMask[BRICK_VOX];     // voxel: scans (bit t - t0) observed in the window
+    __shared__ uint32_t sBase[BRICK_VOX];  // voxel: first live cell
+    __shared__ float sS[BRICK_VOX], sW[BRICK_VOX];
     __shared__ uint16_t sLive[BRICK_VOX];  // live voxels of the window
     // brick's per-scan sample prefix, double-buffered by brick parity: a wave may still read the
     // previous brick's prefix while another writes the next one
@@ -136,19 +112,11 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
     // a batch that overflowed (or follows one) is replayed after the host grows the buffers: its
     // field writes are skipped, everything else (cell clean-up) runs
     const bool commit = !(G->retry && (C->ovf || G->failed));
-    sMask[VOXL(tid)] = 0;
-    sMask[VOXL(tid + 256)] = 0;
-#if TSDF_INT_ZERO_IN_FUSE
-    // every cell starts at zero; each window's fuse chains zero the cells they consumed
-    for (uint32_t j = tid; j < CAP; j += INT_THREADS) {
-        cA[j] = 0ull;
-        cB[j] = 0;
-    }
-#endif
+    sMask[tid] = 0;
+    sMask[tid + 256] = 0;
     uint32_t nvox = 0, ndirty = 0, par = 0;
 #ifdef TSDF_PHASE_TIMING
     unsigned long long ph[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, t_last = clock64();
-    const unsigned long long t_first = __builtin_amdgcn_s_memrealtime();
     uint32_t nb = 0, nwin = 0;
 #endif
     // Software pipeline over the workgroup's bricks: while brick a is processed, brick a + G's
@@ -288,10 +256,10 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
         float* Sg = Pl.sdf + (size_t)(has_slot ? cur.y : 0) * BRICK_VOX;
         float* Wg = Pl.weight + (size_t)(has_slot ? cur.y : 0) * BRICK_VOX;
         // sS / sW of voxels tid, tid + 256: the previous brick's last readers are past a barrier
-        sS[VOXL(tid)] = B.s0;
-        sS[VOXL(tid + 256)] = B.s1;
-        sW[VOXL(tid)] = B.w0;
-        sW[VOXL(tid + 256)] = B.w1;
+        sS[tid] = B.s0;
+        sS[tid + 256] = B.s1;
+        sW[tid] = B.w0;
+        sW[tid + 256] = B.w1;
         uint32_t dirty = 0;  // voxels 2 tid, 2 tid + 1 (bits 0, 1)
         PHASE(0);
         __syncthreads();  // s_cs, sS, sW visible
@@ -331,28 +299,19 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
 #else
                     if (w < nw)
 #endif
-                        atomicOr(&sMask[VOXL(c[j].y & 511u)], (MaskT)1 << w);
+                        atomicOr(&sMask[c[j].y & 511u], (MaskT)1 << w);
                 }
             }
             __syncthreads();
             PHASE(3);
             // P2: live cells and live voxels (packed block scan: cells | voxels << 16)
             {
-                const MaskT m0 = sMask[VOXL(2 * tid)], m1 = sMask[VOXL(2 * tid + 1)];
-                const uint32_t c0 = MASK_POPC(m0), c1 = MASK_POPC(m1);
+                const MaskT m0 = sMask[2 * tid], m1 = sMask[2 * tid + 1];
+                const uint32_t c0 = __popcll(m0), c1 = __popcll(m1);
                 const uint32_t v0 = m0 ? 1u : 0u, v1 = m1 ? 1u : 0u;
                 dirty |= v0 | (v1 << 1);
                 const uint32_t x = (c0 + c1) | ((v0 + v1) << 16);
-#ifdef TSDF_SHFL_SCAN
-                uint32_t incl = x;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const uint32_t y = __shfl_up(incl, d, 64);
-                    if (lane >= d) incl += y;
-                }
-#else
                 const uint32_t incl = wave_incl_scan(x);
-#endif
                 if (lane == 63) s_red[wid] = incl;
                 __syncthreads();
                 uint32_t off = 0, tot = 0;
@@ -364,8 +323,8 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
                 }
                 const uint32_t ex = incl - x + off;
                 const uint32_t cb = ex & 0xFFFFu, vb = ex >> 16;
-                sBase[VOXL(2 * tid)] = cb;
-                sBase[VOXL(2 * tid + 1)] = cb + c0;
+                sBase[2 * tid] = cb;
+                sBase[2 * tid + 1] = cb + c0;
                 if (v0) sLive[vb] = (uint16_t)(2 * tid);
                 if (v1) sLive[vb + v0] = (uint16_t)(2 * tid + 1);
                 if (tid == 0) {
@@ -373,13 +332,11 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
                     s_ncell = tot & 0xFFFFu;
                     nvox += tot & 0xFFFFu;  // (voxel, scan) updates of the window
                 }
-#if !TSDF_INT_ZERO_IN_FUSE
                 // the window's cells start at zero (the previous window's P4 is past a barrier)
                 for (uint32_t j = tid; j < (tot & 0xFFFFu); j += INT_THREADS) {
                     cA[j] = 0ull;
                     cB[j] = 0;
                 }
-#endif
             }
             __syncthreads();
             PHASE(4);
@@ -392,8 +349,8 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
                 for (int j = 0; j < NSLOT; j++) {
                     const uint32_t w = (c[j].y >> 9) - t0;
                     if (w < nw) {
-                        const uint32_t l = VOXL(c[j].y & 511u);
-                        const uint32_t cell = sBase[l] + MASK_POPC(sMask[l] & (((MaskT)1 << w) - 1));
+                        const uint32_t l = c[j].y & 511u;
+                        const uint32_t cell = sBase[l] + __popcll(sMask[l] & (((MaskT)1 << w) - 1));
                         const float sv = __uint_as_float(c[j].x);
                         if constexpr (VB) {
                             float wv;
@@ -420,13 +377,9 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
             if (FUSED ? p1 < pend : q1 < n) load_chunk(ck1);
             __syncthreads();
             PHASE(5);
-#ifndef TSDF_FUSE_P4A
             // VDBFusion: the chains convert their raw cells themselves, two steps ahead of use
             // (off the chain's critical path), so there is no conversion pass and no barrier
             constexpr bool inline_cvt = SEM == 0;
-#else
-            constexpr bool inline_cvt = false;
-#endif
             // P4a: convert every live cell to (A 2^-32, B) in f32, in parallel, so the serial
             // per-voxel chains below are one LDS read, a multiply-add and a division per step
             if constexpr (!inline_cvt) {
@@ -452,9 +405,9 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
                 const uint32_t nlive = s_nlive;
 #endif
                 for (uint32_t vi = tid; vi < nlive; vi += INT_THREADS) {
-                    const uint32_t l = VOXL(sLive[vi]);
+                    const uint32_t l = sLive[vi];
                     const uint32_t cell = sBase[l];
-                    const uint32_t rem = MASK_POPC(sMask[l]);
+                    const uint32_t rem = __popcll(sMask[l]);
                     sMask[l] = 0;
                     float s = sS[l], wt = sW[l];
                     if constexpr (inline_cvt) {
@@ -483,14 +436,6 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
                             a1 = na1;
                             b0 = nb0;
                             b1 = nb1;
-#if TSDF_INT_ZERO_IN_FUSE
-                            cA[cell + k] = 0ull;  // consumed (read two steps ago)
-                            cB[cell + k] = 0;
-                            if (more) {
-                                cA[cell + k + 1] = 0ull;
-                                cB[cell + k + 1] = 0;
-                            }
-#endif
                         }
                         sS[l] = s;
                         sW[l] = wt;
@@ -537,14 +482,6 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
                         }
                         va = make_float2(__uint_as_float((uint32_t)na), __uint_as_float((uint32_t)(na >> 32)));
                         vb = make_float2(__uint_as_float((uint32_t)nb), __uint_as_float((uint32_t)(nb >> 32)));
-#if TSDF_INT_ZERO_IN_FUSE
-                        cA[cell + k] = 0ull;  // consumed (cF aliases cA)
-                        cB[cell + k] = 0;
-                        if (k + 1 < rem) {
-                            cA[cell + k + 1] = 0ull;
-                            cB[cell + k + 1] = 0;
-                        }
-#endif
                     }
                     sS[l] = s;
                     sW[l] = wt;
@@ -556,12 +493,12 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
         }
         if (has_slot && commit) {
             if (dirty & 1u) {
-                Sg[2 * tid] = sS[VOXL(2 * tid)];
-                Wg[2 * tid] = sW[VOXL(2 * tid)];
+                Sg[2 * tid] = sS[2 * tid];
+                Wg[2 * tid] = sW[2 * tid];
             }
             if (dirty & 2u) {
-                Sg[2 * tid + 1] = sS[VOXL(2 * tid + 1)];
-                Wg[2 * tid + 1] = sW[VOXL(2 * tid + 1)];
+                Sg[2 * tid + 1] = sS[2 * tid + 1];
+                Wg[2 * tid + 1] = sW[2 * tid + 1];
             }
         }
         ndirty += __popc(dirty);
@@ -575,14 +512,7 @@ __global__ __launch_bounds__(INT_THREADS, TSDF_INT_WAVES) void k_integrate(Batch
         __syncthreads();  // write-back reads of sS / sW done before the next brick stages its own
     }
 #ifdef TSDF_PHASE_TIMING
-#ifdef TSDF_PHASE_ALL
-    if (tid == 0)
-        printf("wg %u bricks %u total %llu start %llu\n", blockIdx.x, nb,
-               ph[0] + ph[1] + ph[2] + ph[3] + ph[4] + ph[5] + ph[6] + ph[7] + ph[8], t_first);
-    if (false)
-#else
     if (tid == 0 && (blockIdx.x % 97) == 0)
-#endif
         printf("phase blk %u bricks %u windows %u meta %llu bar0 %llu load %llu mask %llu scan %llu "
                "acc %llu conv %llu fuse %llu tail %llu\n", blockIdx.x, nb, nwin, ph[0], ph[1], ph[2],
                ph[3], ph[4], ph[5], ph[8], ph[6], ph[7]);

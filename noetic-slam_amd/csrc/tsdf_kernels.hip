@@ -1,6 +1,6 @@
 // tsdf_kernels.hip — gfx950 kernels of the TSDF integration hot path (MAP_BACKEND_IDX = 4).
 //
-// One launch sequence integrates a BATCH of up to 64 consecutive scans:
+// One launch sequence integrates a BATCH of up to MAX_BATCH consecutive scans:
 //   k_count     one workgroup per 1024 consecutive rays of one scan: every lane walks its rays' DDA
 //               over the truncation band; each distinct brick a ray updates goes into the
 //               workgroup's LDS hash (one LDS CAS + one LDS atomicAdd per (ray, brick) pair, which
@@ -43,18 +43,12 @@ namespace tsdf {
 // physical p = 8 r + x takes logical block G x + r: XCD x gets G contiguous wedges (a full scan's
 // 128 k_count blocks are one group of 8 x 16; its 256 k_place halves one group of 8 x 32), and the
 // same wedges of every scan.  Measured: k_place 0.419 -> 0.404 ms, 50.9 k -> 51.8-52.2 k scans/s
-// (profiles/r03/xcd/; TSDF_NO_XCD_WEDGE builds the plain order).
+// (profiles/r03/xcd/).
 __device__ __forceinline__ uint32_t xcd_wedge(uint32_t p, uint32_t n, uint32_t G) {
-#ifndef TSDF_NO_XCD_WEDGE
     const uint32_t grp = 8u * G, g0 = p - p % grp;
     if (g0 + grp > n) return p;  // the last, partial group keeps its order
     const uint32_t i = p - g0;
     return g0 + (i % 8u) * G + i / 8u;
-#else
-    (void)n;
-    (void)G;
-    return p;
-#endif
 }
 
 // LDS brick hash of one k_count workgroup: slot index of key (inserted if new), -1 when no slot
@@ -78,10 +72,6 @@ __device__ __forceinline__ int lds_insert(unsigned long long* s_key, uint64_t ke
 // must call it; the slots may be reused after the next barrier.
 template <int NT>
 __device__ __forceinline__ bool block_any(bool p, uint32_t* s_vote) {
-#ifdef TSDF_SYNC_OR
-    (void)s_vote;
-    return __syncthreads_or(p);
-#else
     const uint32_t w = __any(p) ? 1u : 0u;
     if ((threadIdx.x & 63) == 0) s_vote[threadIdx.x >> 6] = w;
     __syncthreads();
@@ -89,15 +79,11 @@ __device__ __forceinline__ bool block_any(bool p, uint32_t* s_vote) {
 #pragma unroll
     for (int k = 0; k < NT / 64; k++) r |= s_vote[k];
     return r != 0;
-#endif
 }
 
 // ------------------------------------------------------------------------------------------------
 // k_count
 
-#ifndef TSDF_CNT_THREADS
-#define TSDF_CNT_THREADS 256
-#endif
 // Diagnostic build only (-DTSDF_CNT_PHASE, never shipped): thread 0 of every 61st k_count
 // workgroup prints its wall-clock cycles per phase (walk and pair emission summed over its rays).
 #ifdef TSDF_CNT_PHASE
@@ -112,39 +98,29 @@ __device__ __forceinline__ bool block_any(bool p, uint32_t* s_vote) {
     do {       \
     } while (0)
 #endif
-constexpr int CNT_THREADS = TSDF_CNT_THREADS;
+constexpr int CNT_THREADS = 256;
 
 // NT: threads per workgroup (1024 for batches too small to fill the chip, one ray per lane, so
 // each SIMD holds four waves of one workgroup).  G: RPB-ray blocks per workgroup.  G = 2 (the
-// default for full batches) takes two adjacent blocks of a scan in one 512-lane
-// workgroup with one LDS brick hash, so a brick both wedges reach costs ONE global probe and ONE
-// cell atomic instead of two (runs per 64-scan launch ~5.2 M -> ~3.7 M).  The run lists, staging
-// plans and pair codes stay per (block, half), exactly as k_place reads them; a brick's LDS slot
-// counts its samples in 2G 16-bit sub-counters, one per (block, half).  Two blocks of different
-// scans (a scan with an odd block count) keep their bricks apart by a block bit in the LDS key.
-template <int SEM, int NT = CNT_THREADS, int G = 1>
+// run-time option TSDF_COUNT_PAIRED=1; off by default, measured slower: DESIGN.md §10) takes two
+// adjacent blocks of a scan in one 512-lane workgroup with one LDS brick hash, so a brick both
+// wedges reach costs ONE global probe and ONE cell atomic instead of two (runs per 64-scan launch
+// ~5.2 M -> ~3.7 M).  The run lists, staging plans and pair codes stay per (block, half), exactly
+// as k_place reads them; a brick's LDS slot counts its samples in 2G 16-bit sub-counters, one per
+// (block, half).  Two blocks of different scans (a scan with an odd block count) keep their bricks
+// apart by a block bit in the LDS key.
+//
 // TSDF_SEM_VDBFUSION_F64: the fp32 filter's rare double branch would lift k_count to 93 VGPRs (5
 // waves per SIMD); the bound keeps the LDS-limited 6, spilling only inside that branch
-#ifndef TSDF_F64_COUNT_WAVES
-#define TSDF_F64_COUNT_WAVES 6
-#endif
-#ifndef TSDF_F64_PLACE_WAVES
-#define TSDF_F64_PLACE_WAVES 1
-#endif
-__global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? TSDF_F64_COUNT_WAVES : 1) void k_count(const float* __restrict__ xyz, BatchRef D,
+constexpr int F64_COUNT_WAVES = 6, F64_PLACE_WAVES = 1;
+template <int SEM, int NT = CNT_THREADS, int G = 1>
+__global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? F64_COUNT_WAVES : 1) void k_count(const float* __restrict__ xyz, BatchRef D,
                                                       RayConst R, Table T, Work Wk, Globals* G_,
                                                       int parity) {
     static_assert(G == 1 || G == 2, "one or two blocks per workgroup");
     static_assert(G == 1 || RPB % NT == 0, "a pass over the rays stays inside one block");
     using CntT = typename std::conditional<G == 2, unsigned long long, uint32_t>::type;
     constexpr int PCAP = plan_cap(SEM), PW = plan_words(SEM);  // k_place<SEM>'s staging plan
-#ifdef TSDF_CNT_SPLIT
-    // variant build: the global phase (find-or-insert, cell atomic) runs in k_resolve
-    constexpr bool SPLIT = G == 1;
-#else
-    constexpr bool SPLIT = false;
-#endif
-    __shared__ uint32_t s_wsl[SPLIT ? NT / 64 : 1];
     constexpr int NSUB = 2 * G;  // (block, half) sub-runs
     constexpr uint64_t KEY_G1 = 1ull << 63;  // LDS key bit: block 1 of a workgroup spanning two scans
     __shared__ unsigned long long s_key[HCAP];
@@ -351,12 +327,10 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? TSD
         key[j] = g1 ? lk & ~KEY_G1 : lk;
         ts[j] = g1 ? tb[G - 1] : tb[0];
     };
-    if constexpr (!SPLIT) {
 #pragma unroll
-        for (int j = 0; j < SPT; j++) {
-            slot_key(j);
-            k0[j] = key[j] != EMPTY_KEY ? T.keys[mix64(key[j]) & T.mask] : EMPTY_KEY;
-        }
+    for (int j = 0; j < SPT; j++) {
+        slot_key(j);
+        k0[j] = key[j] != EMPTY_KEY ? T.keys[mix64(key[j]) & T.mask] : EMPTY_KEY;
     }
     // one dense run list per (block, half): k_place workgroup 2 b + half
     uint32_t ns[NSUB], cc[G];
@@ -375,16 +349,9 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? TSD
             cc[s >> 1] += (n ? 1u : 0u) << (16 * (s & 1));
         }
     }
-    uint32_t nsl = 0, rbase = 0;  // SPLIT: the thread's distinct bricks, their first record
-    if constexpr (SPLIT) {
-#pragma unroll
-        for (int j = 0; j < SPT; j++) nsl += s_key[threadIdx.x * SPT + j] != EMPTY_KEY ? 1u : 0u;
-    }
     uint32_t off[NSUB], idx[NSUB];
     {
         const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        const uint32_t isl = SPLIT ? wave_incl_scan(nsl) : 0u;
-        if (SPLIT && lane == 63) s_wsl[wid] = isl;
         uint32_t in[NSUB], ic[G];
 #pragma unroll
         for (int s = 0; s < NSUB; s++) in[s] = wave_incl_scan(ns[s]);
@@ -398,15 +365,6 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? TSD
             }
         }
         __syncthreads();
-        if constexpr (SPLIT) {
-            uint32_t ex = 0, tot = 0;
-            for (int w = 0; w < NT / 64; w++) {
-                ex += w < wid ? s_wsl[w] : 0u;
-                tot += s_wsl[w];
-            }
-            rbase = ex + isl - nsl;
-            if (threadIdx.x == NT - 1) Wk.rsv_n[bx] = tot;
-        }
 #pragma unroll
         for (int g = 0; g < G; g++) {
             unsigned long long ex = 0, tot = 0;
@@ -434,36 +392,6 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? TSD
         }
     }
     CPH(4);  // block scan
-    if constexpr (SPLIT) {
-        // one record per distinct brick for k_resolve, which fills the runs' (table index, cell
-        // rank); this kernel writes the runs' (offset, samples | slot) and the run-start bits
-        static_assert(G == 1 && HCAP <= 2048 && MAX_BATCH <= 1024, "record packing");
-        uint32_t r = rbase;
-#pragma unroll
-        for (int j = 0; j < SPT; j++) {
-            const int slot = threadIdx.x * SPT + j;
-            slot_key(j);
-            if (key[j] == EMPTY_KEY) continue;
-            const uint32_t c = (uint32_t)s_cnt[slot], n0 = c & 0xFFFFu, n1 = c >> 16;
-            uint32_t w = ts[j] << 22;
-            uint4* bt = Wk.blk + (size_t)(2 * bx) * HCAP;
-            if (n0) {
-                reinterpret_cast<uint2*>(bt + idx[0])[1] = make_uint2(off[0], n0 | ((uint32_t)slot << 16));
-                if (off[0] < (uint32_t)PCAP) atomicOr(&s_bm[0][off[0] >> 5], 1u << (off[0] & 31));
-                w |= idx[0]++;
-                off[0] += n0;
-            }
-            if (n1) {
-                reinterpret_cast<uint2*>(bt + HCAP + idx[NSUB - 1])[1] =
-                    make_uint2(off[NSUB - 1], n1 | ((uint32_t)slot << 16));
-                if (off[NSUB - 1] < (uint32_t)PCAP)
-                    atomicOr(&s_bm[NSUB - 1][off[NSUB - 1] >> 5], 1u << (off[NSUB - 1] & 31));
-                w |= idx[NSUB - 1]++ << 11;
-                off[NSUB - 1] += n1;
-            }
-            Wk.rsv[(size_t)bx * HCAP + r++] = make_uint4((uint32_t)key[j], (uint32_t)(key[j] >> 32), c, w);
-        }
-    } else {
     int64_t hx[SPT];
 #pragma unroll
     for (int j = 0; j < SPT; j++) {
@@ -534,7 +462,6 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? TSD
             }
         }
     }
-    }  // !SPLIT
     CPH(6);  // cell atomics + run lists
     // k_place's staging plan for each (block, half): the run-start bitmap and its exclusive
     // popcount prefix per word (wave s writes sub-run list s's)
@@ -590,43 +517,6 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? TSD
 #endif
 }
 
-#ifdef TSDF_CNT_SPLIT
-// k_resolve (TSDF_CNT_SPLIT variant): k_count's global phase as its own launch, so the LDS-bound
-// k_count workgroups do not hold their LDS through the find-or-insert and cell-atomic round trips.
-// One workgroup per k_count block, one lane per distinct brick of the block's LDS hash: find or
-// insert the brick, reserve its samples in the (brick, scan) cell, and write the (table index,
-// cell rank) half of the block's run records.
-constexpr int RSV_THREADS = 256;
-__global__ __launch_bounds__(RSV_THREADS) void k_resolve(BatchRef D, RayConst R, Table T, Work Wk,
-                                                        Globals* G, int parity) {
-    Counters* C = &G->ctr[parity];
-    uint32_t b = blockIdx.x;
-    if (R.sec_on) {
-        if (blockIdx.x >= C->n_act) return;
-        b = Wk.act[blockIdx.x];
-    }
-    if (b >= D.n_blocks) return;
-    const uint32_t n = Wk.rsv_n[b];
-    const uint4* rec = Wk.rsv + (size_t)b * HCAP;
-    uint4* bt = Wk.blk + (size_t)(2 * b) * HCAP;
-    for (uint32_t i = threadIdx.x; i < n; i += RSV_THREADS) {
-        const uint4 q = rec[i];
-        const uint64_t key = (uint64_t)q.x | ((uint64_t)q.y << 32);
-        const uint32_t n0 = q.z & 0xFFFFu, n1 = q.z >> 16, t = q.w >> 22;
-        const uint64_t h0 = mix64(key) & T.mask;
-        const int64_t hx = T.keys[h0] == key ? (int64_t)h0 : table_insert(T, key, &C->ovf);
-        uint32_t tx = NO_PAIR, rk = 0u;
-        if (hx >= 0) {
-            tx = (uint32_t)hx;
-            rk = atomicAdd(&T.cell[(size_t)hx * T.cell_stride + t], n0 + n1);
-            if (rk == 0u) T.touched[tx] = 1u;
-        }
-        if (n0) reinterpret_cast<uint2*>(bt + (q.w & 2047u))[0] = make_uint2(tx, rk);
-        if (n1) reinterpret_cast<uint2*>(bt + HCAP + ((q.w >> 11) & 2047u))[0] = make_uint2(tx, rk + n0);
-    }
-}
-#endif
-
 // ------------------------------------------------------------------------------------------------
 // k_sector_flags (sector sharding only): one wave per k_count block of RPB rays, 16 points per lane,
 // a wave vote; no LDS, so the pass runs at full occupancy and the walk kernels' blocks of other
@@ -665,11 +555,9 @@ hipError_t launch_sector_flags(const float* d_xyz, const BatchRef& D, const RayC
 // is whatever the atomics give: each brick is fused independently, so the field does not depend
 // on it.  k_compact builds the sorted list as it writes the records: k_compact_sum counts the
 // (table slice, size class) histogram, k_compact_scan turns it into first positions, and
-// k_compact_write ranks each record in its (slice, class) with one global atomic (a separate
-// three-launch k_order remains for the ablation build TSDF_SEPARATE_ORDER).
+// k_compact_write ranks each record in its (slice, class) with one global atomic.
 
-constexpr int ORD_THREADS = 256;
-constexpr int ORD_BLOCKS = 64;  // slices: of the active list (k_order), of the table's chunks (k_compact)
+constexpr int ORD_BLOCKS = 64;  // slices of the table's chunks
 constexpr int ORD_CLASSES = 32;
 
 __device__ __forceinline__ uint32_t size_class(uint32_t n) {
@@ -766,10 +654,8 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_sum(uint32_t n_scans, T
         s_acc[0] = 0u;
         s_acc[1] = 0u;
     }
-#ifndef TSDF_SEPARATE_ORDER
     __shared__ uint32_t s_cls[ORD_CLASSES];  // the chunk's bricks per size class
     if (threadIdx.x < ORD_CLASSES) s_cls[threadIdx.x] = 0u;
-#endif
     const uint32_t nh = compact_list(T, blockIdx.x * CMP_CHUNK, s_h, s_w, false);
     const uint32_t nq = row_groups<FUSED>(n_scans);  // whole uint4 groups (see cell_stride)
     const uint32_t grp = threadIdx.x / CMP_GROUP, li = threadIdx.x % CMP_GROUP;
@@ -780,11 +666,9 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_sum(uint32_t n_scans, T
         uint32_t sum = 0;
         for (uint32_t q = li; q < nq; q += CMP_GROUP) sum += group_count<FUSED>(cp[q]);
         samples += sum;
-#ifndef TSDF_SEPARATE_ORDER
 #pragma unroll
         for (int d = CMP_GROUP / 2; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, CMP_GROUP);
         if (li == 0) atomicAdd(&s_cls[size_class(sum)], 1u);
-#endif
         if (li == 0 && T.slots[h] == UNASSIGNED) nnew++;
     }
     samples = wave_sum<uint32_t>(samples);
@@ -795,12 +679,10 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_sum(uint32_t n_scans, T
     }
     __syncthreads();
     if (threadIdx.x == 0) Wk.cagg[blockIdx.x] = make_uint4(nh, s_acc[0], s_acc[1], 0u);
-#ifndef TSDF_SEPARATE_ORDER
     // the chunk's slice histogram (zeroed again by k_compact_scan once read)
     if (threadIdx.x < ORD_CLASSES && s_cls[threadIdx.x])
         atomicAdd(&Wk.ord_hist[ord_chunk_slice(blockIdx.x, gridDim.x) * ORD_CLASSES + threadIdx.x],
                   s_cls[threadIdx.x]);
-#endif
 }
 
 __global__ __launch_bounds__(CMP_SCAN_THREADS) void k_compact_scan(uint32_t nch, Work Wk,
@@ -864,11 +746,10 @@ __global__ __launch_bounds__(CMP_SCAN_THREADS) void k_compact_scan(uint32_t nch,
         s_carry[2] += tn;
     }
     __syncthreads();
-#ifndef TSDF_SEPARATE_ORDER
     // size order: (slice, class) first positions = the records of larger classes + class k's
-    // records in the slices before (k_order_scan's rule); the histogram is zeroed for the next
-    // batch.  Wave w takes classes w and w + 16 with lane = slice (ORD_BLOCKS = 64): one DPP scan
-    // per class gives the slices' prefix, wave 0 the classes' bases.
+    // records in the slices before; the histogram is zeroed for the next batch.  Wave w takes
+    // classes w and w + 16 with lane = slice (ORD_BLOCKS = 64): one DPP scan per class gives the
+    // slices' prefix, wave 0 the classes' bases.
     static_assert(ORD_BLOCKS == 64 && ORD_CLASSES == 32 && CMP_SCAN_THREADS == 1024, "layout");
     {
         __shared__ uint32_t s_tot[ORD_CLASSES], s_cbase[ORD_CLASSES];
@@ -896,7 +777,6 @@ __global__ __launch_bounds__(CMP_SCAN_THREADS) void k_compact_scan(uint32_t nch,
             Wk.ord_hist[ORD_BLOCKS * ORD_CLASSES + lane * ORD_CLASSES + cls] = s_cbase[cls] + ex[q];
         }
     }
-#endif
     if (threadIdx.x == 0) {
         C->n_active = s_carry[0];
         C->cursor = s_carry[1];
@@ -961,12 +841,10 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_write(uint32_t n_scans,
             // k_integrate's whole per-brick header in one record
             const uint4 rec = make_uint4(h, slot, base.y + ec, n[j]);
             if (base.x + k < Wk.max_active) Wk.active[base.x + k] = rec;
-#ifndef TSDF_SEPARATE_ORDER
             const uint32_t op = atomicAdd(&Wk.ord_hist[ORD_BLOCKS * ORD_CLASSES +
                                                        ord_chunk_slice(blockIdx.x, gridDim.x) * ORD_CLASSES +
                                                        size_class(n[j])], 1u);
             if (op < Wk.max_active) Wk.active_ord[op] = rec;
-#endif
             s_n[k] = base.y + ec;
         }
         ec += n[j];
@@ -1033,7 +911,7 @@ __global__ __launch_bounds__(CMP_THREADS) void k_compact_write(uint32_t n_scans,
 constexpr int PLC_THREADS = RPB / 2;  // one ray per lane, half a k_count workgroup's rays
 
 template <int SEM>
-__global__ __launch_bounds__(PLC_THREADS, SEM == 2 ? TSDF_F64_PLACE_WAVES : 1) void k_place(const float* __restrict__ xyz, BatchRef D,
+__global__ __launch_bounds__(PLC_THREADS, SEM == 2 ? F64_PLACE_WAVES : 1) void k_place(const float* __restrict__ xyz, BatchRef D,
                                                       RayConst R, Table T, Work Wk,
                                                       const Globals* __restrict__ G, int parity) {
     // staging capacity (tsdf_device.h plan_cap: Voxblox 1/z^2 stages more, at 8 B a sample);
@@ -1051,20 +929,9 @@ __global__ __launch_bounds__(PLC_THREADS, SEM == 2 ? TSDF_F64_PLACE_WAVES : 1) v
     __shared__ StL st_l[STG];
     __shared__ float s_w0[SEM == 3 ? PLC_THREADS : 1];
     __shared__ uint32_t s_vote[2][PLC_THREADS / 64];  // block_any: sector test, second pass
-#ifdef TSDF_ABLATE_PL_EMPTY
-    __shared__ uint32_t s_nst;             // staged samples (end of the last staged run)
-#endif
 #ifdef TSDF_PLC_PHASE  // diagnostic build: thread 0's clock at the phase boundaries
     unsigned long long pt[6];
     if (threadIdx.x == 0) pt[0] = clock64();
-#endif
-#ifdef TSDF_ABLATE_PL_EMPTY  // diagnostic build: the workgroups' dispatch and LDS allocation only
-    if (threadIdx.x < 2 && D.n_scans == 0xFFFFFFFFu) {
-        s_base[threadIdx.x] = 0u; s_loff[threadIdx.x] = 0; s_ord[threadIdx.x] = 0;
-        s_bits[threadIdx.x] = 0u; s_wpre[threadIdx.x] = 0; st_s[threadIdx.x] = 0.0f;
-        st_l[threadIdx.x] = 0; s_nst = 0u;
-    }
-    return;
 #endif
     // workgroup 2 b + hf takes half hf of k_count block b's rays, and that half's run list
     // (sector sharding: block b is the (w / 2)-th of k_sector_flags' list, the rest leave)
@@ -1145,9 +1012,6 @@ __global__ __launch_bounds__(PLC_THREADS, SEM == 2 ? TSDF_F64_PLACE_WAVES : 1) v
     __syncthreads();
 #ifdef TSDF_PLC_PHASE
     if (threadIdx.x == 0) pt[2] = clock64();
-#endif
-#ifdef TSDF_ABLATE_PL_PROLOGUE  // diagnostic build: the prologue (loads, run tables) only
-    if (D.n_scans != 0xFFFFFFFFu) return;
 #endif
 #ifdef TSDF_PLC_PHASE
     if (threadIdx.x == 0) pt[3] = clock64();
@@ -1452,26 +1316,15 @@ hipError_t launch_count(const float* d_xyz, const BatchRef& D, const RayConst& R
     // plans k_place<3>'s larger staging
     if (wide) {  // a batch too small to fill the chip: 1024-lane workgroups
         auto k = R.sem == 3 ? k_count<3, 1024> : R.sem == 1 ? k_count<1, 1024> : R.sem == 2 ? k_count<2, 1024> : k_count<0, 1024>;
-#ifndef TSDF_CNT_SPLIT
         tlaunch(k, D.n_blocks, 1024, st, kt.start, kt.stop, d_xyz, D, R, T, Wk, G, parity);
-#else
-        tlaunch(k, D.n_blocks, 1024, st, kt.start, nullptr, d_xyz, D, R, T, Wk, G, parity);
-#endif
     } else if (paired) {  // two blocks per 512-lane workgroup (no sector sharding)
         constexpr int NT2 = 2 * CNT_THREADS;
         auto k = R.sem == 3 ? k_count<3, NT2, 2> : R.sem == 1 ? k_count<1, NT2, 2> : R.sem == 2 ? k_count<2, NT2, 2> : k_count<0, NT2, 2>;
         tlaunch(k, (D.n_blocks + 1) / 2, NT2, st, kt.start, kt.stop, d_xyz, D, R, T, Wk, G, parity);
     } else {
         auto k = R.sem == 3 ? k_count<3> : R.sem == 1 ? k_count<1> : R.sem == 2 ? k_count<2> : k_count<0>;
-#ifndef TSDF_CNT_SPLIT
         tlaunch(k, D.n_blocks, CNT_THREADS, st, kt.start, kt.stop, d_xyz, D, R, T, Wk, G, parity);
-#else
-        tlaunch(k, D.n_blocks, CNT_THREADS, st, kt.start, nullptr, d_xyz, D, R, T, Wk, G, parity);
-#endif
     }
-#ifdef TSDF_CNT_SPLIT
-    if (!paired) tlaunch(k_resolve, D.n_blocks, RSV_THREADS, st, nullptr, kt.stop, D, R, T, Wk, G, parity);
-#endif
     return hipGetLastError();
 }
 
@@ -1490,76 +1343,6 @@ hipError_t launch_place(const float* d_xyz, const BatchRef& D, const RayConst& R
                         const Work& Wk, Globals* G, int parity, hipStream_t st, const KTime& kt) {
     auto k = R.sem == 1 ? k_place<1> : R.sem == 3 ? k_place<3> : R.sem == 2 ? k_place<2> : k_place<0>;
     tlaunch(k, 2 * D.n_blocks, PLC_THREADS, st, kt.start, kt.stop, d_xyz, D, R, T, Wk, G, parity);
-    return hipGetLastError();
-}
-
-__device__ __forceinline__ void ord_slice(uint32_t n_active, uint32_t b, uint32_t& i0,
-                                          uint32_t& i1) {
-    const uint32_t per = (n_active + ORD_BLOCKS - 1) / ORD_BLOCKS;
-    i0 = min(n_active, b * per);
-    i1 = min(n_active, i0 + per);
-}
-
-// pass 1: per-slice class histogram (LDS), written out without global atomics
-__global__ __launch_bounds__(ORD_THREADS) void k_order_hist(Work Wk, Globals* G, int parity) {
-    __shared__ uint32_t h[ORD_CLASSES];
-    if (threadIdx.x < ORD_CLASSES) h[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t i0, i1;
-    ord_slice(min(G->ctr[parity].n_active, Wk.max_active), blockIdx.x, i0, i1);
-    for (uint32_t i = i0 + threadIdx.x; i < i1; i += ORD_THREADS)
-        atomicAdd(&h[size_class(Wk.active[i].w)], 1u);
-    __syncthreads();
-    if (threadIdx.x < ORD_CLASSES) Wk.ord_hist[blockIdx.x * ORD_CLASSES + threadIdx.x] = h[threadIdx.x];
-}
-
-// pass 2 (one workgroup): slice s's first position in class k = all records of larger classes +
-// class k's records in the slices before s
-__global__ __launch_bounds__(ORD_BLOCKS * ORD_CLASSES / 2) void k_order_scan(Work Wk) {
-    constexpr int NT = ORD_BLOCKS * ORD_CLASSES / 2;  // two (slice, class) entries per thread
-    __shared__ uint32_t tot[ORD_CLASSES];
-    __shared__ uint32_t cls_base[ORD_CLASSES];
-    const int t = threadIdx.x;
-    if (t < ORD_CLASSES) {
-        uint32_t sum = 0;  // class t over all slices
-        for (int b = 0; b < ORD_BLOCKS; b++) sum += Wk.ord_hist[b * ORD_CLASSES + t];
-        tot[t] = sum;
-    }
-    __syncthreads();
-    if (t < 64) {
-        const uint32_t v = t < ORD_CLASSES ? tot[t] : 0u;
-        const uint32_t incl = wave_incl_scan(v);
-        if (t < ORD_CLASSES) cls_base[t] = incl - v;
-    }
-    __syncthreads();
-    if (t < ORD_CLASSES) {  // running prefix over the slices of class t
-        uint32_t run = cls_base[t];
-        for (int b = 0; b < ORD_BLOCKS; b++) {
-            const uint32_t v = Wk.ord_hist[b * ORD_CLASSES + t];
-            Wk.ord_hist[b * ORD_CLASSES + t] = run;
-            run += v;
-        }
-    }
-    (void)NT;
-}
-
-// pass 3: every record to its class position (rank inside a slice's class from LDS atomics)
-__global__ __launch_bounds__(ORD_THREADS) void k_order_scatter(Work Wk, Globals* G, int parity) {
-    __shared__ uint32_t base[ORD_CLASSES];
-    if (threadIdx.x < ORD_CLASSES) base[threadIdx.x] = Wk.ord_hist[blockIdx.x * ORD_CLASSES + threadIdx.x];
-    __syncthreads();
-    uint32_t i0, i1;
-    ord_slice(min(G->ctr[parity].n_active, Wk.max_active), blockIdx.x, i0, i1);
-    for (uint32_t i = i0 + threadIdx.x; i < i1; i += ORD_THREADS) {
-        const uint4 r = Wk.active[i];
-        Wk.active_ord[atomicAdd(&base[size_class(r.w)], 1u)] = r;
-    }
-}
-
-hipError_t launch_order(const Work& Wk, Globals* G, int parity, hipStream_t st) {
-    k_order_hist<<<ORD_BLOCKS, ORD_THREADS, 0, st>>>(Wk, G, parity);
-    k_order_scan<<<1, ORD_BLOCKS * ORD_CLASSES / 2, 0, st>>>(Wk);
-    k_order_scatter<<<ORD_BLOCKS, ORD_THREADS, 0, st>>>(Wk, G, parity);
     return hipGetLastError();
 }
 

@@ -633,9 +633,6 @@ __device__ __forceinline__ void vdb_geom(const RayConst& R, const VdbState& r, d
     // the point's double conversions are loop-invariant: the compiler hoists them out of the walk
     // (4 more VGPRs in k_place, whose occupancy LDS sets; 3 double conversions less per DDA step)
     float px = r.px, py = r.py, pz = r.pz;
-#ifdef TSDF_F64_PER_VOXEL_P
-    asm volatile("" : "+v"(px), "+v"(py), "+v"(pz));
-#endif
     vdb_geom_at(R.hvs_d, r.oxd, r.oyd, r.ozd, px, py, pz, r.vx, r.vy, r.vz, proj,
                 d2);
 }
@@ -659,18 +656,6 @@ __device__ __forceinline__ bool vdb_gate_filtered(const RayConst& R, float ox, f
     bool g = pos || (neg && in);
     const bool open = !(d2 <= r.bchk) || !(pos || neg) || (neg && !(in || out));
     if (__builtin_expect(__any(open), 0)) {
-#ifdef TSDF_F64_GATE_R05  // A/B only: round 5's branch (8 VGPR spills at the 6-wave bound)
-        if (open) {
-            // the origin, vs / 2 and the point re-read or re-converted here (opaque to hoisting),
-            // so that the rare branch keeps no double live across the walk loop
-            const ScanRec* q = r.sr;
-            float px = r.px, py = r.py, pz = r.pz, vs = R.vs;
-            asm volatile("" : "+v"(q), "+v"(px), "+v"(py), "+v"(pz), "+v"(vs));
-            double pd, dd;
-            vdb_geom_at((double)vs * 0.5, q->odx, q->ody, q->odz, px, py, pz, r.vx, r.vy, r.vz, pd, dd);
-            g = pd > 0.0 || (pd < 0.0 && dd < R.gate_d2);
-        }
-#else
         if (open) {
             // the origin, vs / 2 and the point re-read or re-converted here (opaque to hoisting),
             // so that the rare branch keeps no double live across the walk loop
@@ -707,7 +692,6 @@ __device__ __forceinline__ bool vdb_gate_filtered(const RayConst& R, float ox, f
             dd = b * b + dd;
             g = (pd > 0.0) | ((pd < 0.0) & (dd < R.gate_d2));
         }
-#endif
     }
     return g;
 }

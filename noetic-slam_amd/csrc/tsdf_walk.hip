@@ -150,9 +150,6 @@ __global__ __launch_bounds__(WLK_THREADS) void k_walk(const float* __restrict__ 
         }
     };
     // rays far from the index-domain edge (all, in practice) skip the per-voxel check
-#ifdef TSDF_ABLATE_WALK_NOWALK  // diagnostic build: no walk (wrong results)
-    live = false;
-#endif
     if (__all(!ok || Walk<SEM>::inside(R, r))) walk(std::false_type{});
     else walk(std::true_type{});
     // a walk longer than the host's bound, or more than 4 bricks: never for eligible parameters
@@ -240,11 +237,7 @@ __global__ __launch_bounds__(WLK_THREADS) void k_walk(const float* __restrict__ 
 #pragma unroll
     for (int j = 0; j < SPT; j++) {
         hx[j] = -1;
-#ifdef TSDF_ABLATE_WALK_NOGLOBAL  // diagnostic build: no global table work (wrong results)
-        if (key[j] != EMPTY_KEY && key[j] == 12345ull)
-#else
         if (key[j] != EMPTY_KEY)
-#endif
             hx[j] = k0[j] == key[j] ? (int64_t)h0[j] : table_insert(T, key[j], &C->ovf);
     }
     unsigned long long* cell64 = reinterpret_cast<unsigned long long*>(T.cell);
@@ -278,14 +271,12 @@ __global__ __launch_bounds__(WLK_THREADS) void k_walk(const float* __restrict__ 
     __syncthreads();  // staging complete
     // copy-out: the workgroup's samples, linear, to its region (full lines)
     const size_t region = (size_t)blockIdx.x * STG;
-#ifndef TSDF_ABLATE_WALK_NOCOPY  // diagnostic build: no copy-out (wrong results)
     if (region + STG <= Wk.max_smp) {
         for (uint32_t q = threadIdx.x; q < tot_s; q += WLK_THREADS)
             Wk.smp[region + q] = make_uint2(__float_as_uint(st_s[q]), (t << 9) | st_l[q]);
     } else if (threadIdx.x == 0) {
         atomicOr(&C->ovf, OVF_SMP);  // region array too small (sector sharding): grow and replay
     }
-#endif
     // stats: one atomic per block on a shard picked by block index
     unsigned long long v = wave_sum<unsigned long long>(ok ? 1ull : 0ull);
     unsigned long long q = wave_sum<unsigned long long>((unsigned long long)np);
