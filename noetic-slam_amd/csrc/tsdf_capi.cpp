@@ -244,6 +244,7 @@ struct Capacity {
 // Voxblox MergedTsdfIntegrator only, tsdf_merged.hip)
 struct Lane {
     DevBuf<uint32_t> pair, blk_n, plan, spn, ord_hist, act;
+    DevBuf<uint32_t> tile;  // per scan of the batch: its ray tiles' column height (k_tile_detect)
     DevBuf<uint4> blk, fb;
     DevBuf<uint2> smp;
     DevBuf<uint64_t> mg_ekey;
@@ -305,6 +306,11 @@ struct tsdf_ctx {
     // TSDF_COUNT_PAIRED=1: larger batches run k_count with two blocks per 512-lane workgroup
     // (bit-exact, ~29% fewer cell atomics, but measured slower: DESIGN.md §10, round 4)
     bool count_paired = false;
+    // TSDF_RAY_TILES: the walk kernels' blocks as 32 x 32 ray tiles of the scan instead of 1024
+    // consecutive rays (ray_tile.h).  -1 (unset): scans whose points k_tile_detect finds to be
+    // intact columns; 0: never; 64 / 128 / 256: every scan, with this column height.  Off for
+    // sector contexts, the Merged pre-pass and the single walk.
+    int ray_tiles = -1;
     // host-pointer path: pinned double buffer per scan; the pending batch's points are staged in
     // stage2[pend_stage]
     PinBuf<float> h_stage[2];
@@ -493,10 +499,7 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
         HIPCHK(c, hipEventRecord(c->ev_main, c->stream));
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_main, 0));
     }
-    if (prev) HIPCHK(c, hipStreamWaitEvent(st, c->ev_compact[par ^ 1], 0));  // before front: 1, 2
-    c->ht.lap(HT_WAITS);
-    // -- ring upload: the batch's scan records -> the device (a ring slot; the host slot is reused
-    // once its copy ran)
+    // -- the batch's scan records into its host ring slot (reused once the slot's upload ran)
     ScanRing& ring = c->ring;
     const uint64_t seq = ring.next++;
     const int slot = (int)(seq % ScanRing::N);
@@ -506,10 +509,25 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
     ScanRec* ds = ring.dev + at;
     std::memcpy(ring.host + at, D.s, (D.n_scans + 1) * sizeof(ScanRec));
     c->ht.lap(HT_RING_COPY);
+    // -- ray tiles: which scans are intact columns.  k_tile_detect needs only the points and the
+    // scan records, which it reads from the host slot, so it runs ahead of the wait on the previous
+    // batch, beside that batch's kernels.  (The upload stays behind the wait: ahead of it, k_count
+    // started level with the previous batch's k_integrate instead of ~10 us after it, and
+    // k_integrate, whose grid is sized to own the chip, ran 0.58-0.70 ms beside it instead of
+    // 0.38 -- DESIGN.md §10.)
+    const bool tiles = c->ray_tiles != 0 && !c->R.sec_on && !c->idx_rule && !c->merged &&
+                       !c->plan.fused && D.n_blocks != 0;
+    uint32_t* const d_tile = tiles ? c->lane[par].tile.p : nullptr;
+    if (tiles)
+        HIPCHK(c, launch_tile_detect(d_xyz, BatchRef{D.n_scans, D.n_blocks, ring.host_dev + at, nullptr},
+                                     d_tile, c->ray_tiles > 0 ? (uint32_t)c->ray_tiles : 0u, st));
+    if (prev) HIPCHK(c, hipStreamWaitEvent(st, c->ev_compact[par ^ 1], 0));  // before front: 1, 2
+    c->ht.lap(HT_WAITS);
+    // -- ring upload: the records -> the device ring slot
     HIPCHK(c, launch_upload(ring.host_dev + at, ds, (uint32_t)((D.n_scans + 1) * sizeof(ScanRec)),
                             ring.done_dev, seq + 1, st));
     c->ht.lap(HT_UPLOAD);
-    const BatchRef B{D.n_scans, D.n_blocks, ds};
+    const BatchRef B{D.n_scans, D.n_blocks, ds, d_tile};
     // -- pre-pass (MergedTsdfIntegrator): the batch's points bundled per (scan, voxel) first; the
     // walk kernels then read one ray per bundle, in the slot of its first point (tsdf_merged.hip)
     RayConst R = c->R;
@@ -567,7 +585,7 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
         c->ht.lap(HT_INTEGRATE);
     }
     // -- finish and the host's books
-    HIPCHK(c, launch_finish(c->G, par, (uint32_t)c->batch_id, st));
+    HIPCHK(c, launch_finish(c->G, par, (uint32_t)c->batch_id, B, st));
     if (cross) {  // the batch's end: the other stream's next batches wait on it
         HIPCHK(c, hipEventRecord(ring.ev[slot], st));
         c->ev_integ[par] = ring.ev[slot];
@@ -889,12 +907,12 @@ static int emit_metrics(tsdf_ctx* c) {
                 "{\"batch\": %llu, \"scans\": %u, \"points\": %llu, \"rays\": %llu, \"pairs\": %llu, "
                 "\"voxel_updates\": %llu, \"dirty_voxels\": %llu, \"active_bricks\": %u, "
                 "\"new_bricks\": %u, \"bricks\": %u, \"overflow\": %u, \"committed\": %s, "
-                "\"algorithmic_bytes\": %.0f",
+                "\"tiled_scans\": %u, \"algorithmic_bytes\": %.0f",
                 (unsigned long long)b, scans, (unsigned long long)points,
                 (unsigned long long)r.rays, (unsigned long long)r.pairs, (unsigned long long)r.vox,
                 (unsigned long long)r.dirty, r.n_active, r.n_new,
                 std::min<uint32_t>(r.pool_count, c->T.max_bricks), r.ovf,
-                r.committed ? "true" : "false", bytes);
+                r.committed ? "true" : "false", r.tiled, bytes);
         const std::array<double, KIND_N>* ms = nullptr;
         if (c->timer) {
             auto& bm = c->timer->batch_ms;
@@ -1172,6 +1190,7 @@ static int create_impl(tsdf_ctx* c, const tsdf_params* p) {
         HIPCHK(c, L.ord_hist.alloc(2 * 64 * 32));
         HIPCHK(c, hipMemset(L.ord_hist, 0, 2 * 64 * 32 * sizeof(uint32_t)));
         HIPCHK(c, L.act.alloc(c->plan.max_blocks));
+        HIPCHK(c, L.tile.alloc(c->max_batch));
         HIPCHK(c, c->stage2[q].alloc(c->plan.batch_points * 3));
         if (c->merged) {  // the bundling pre-pass: one set per parity, batch_points entries
             const uint64_t n = c->plan.batch_points, nb = mg_buckets_max(n);
@@ -1189,6 +1208,10 @@ static int create_impl(tsdf_ctx* c, const tsdf_params* p) {
     if (const char* e = std::getenv("TSDF_SMALL_NS")) c->small_ns = std::max(0, std::min(8, std::atoi(e)));
     if (const char* e = std::getenv("TSDF_COUNT_WIDE")) c->count_wide = (uint32_t)std::max(0, std::atoi(e));
     if (const char* e = std::getenv("TSDF_COUNT_PAIRED")) c->count_paired = std::atoi(e) != 0;
+    if (const char* e = std::getenv("TSDF_RAY_TILES")) {
+        const int h = std::atoi(e);
+        c->ray_tiles = h == 64 || h == 128 || h == 256 ? h : 0;
+    }
     // host staging threads: 3 workers + the caller (TSDF_PACK_THREADS overrides; 1 = none)
     int nt = 4;
     if (const char* e = std::getenv("TSDF_PACK_THREADS")) nt = std::max(1, std::atoi(e));

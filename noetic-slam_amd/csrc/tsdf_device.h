@@ -46,7 +46,8 @@ constexpr int MAX_BATCH = 512;         // scans per batch
 #ifndef TSDF_HCAP
 #define TSDF_HCAP 2048
 #endif
-constexpr int RPB = TSDF_RPB;          // rays per k_count / k_place block (one scan per block)
+constexpr int RPB = TSDF_RPB;          // rays per k_count / k_place block (one scan per block;
+                                       // which rays: ray_tile.h)
 constexpr int HCAP = TSDF_HCAP;        // LDS brick-hash slots per k_count block (~300-800 used)
 constexpr int LDS_PROBES = 64;         // probe limit before a pair takes the global fallback
 constexpr int MAX_IN_BRICK = 22;       // a line visits at most 8+8+8-2 voxels of an 8^3 brick
@@ -182,6 +183,9 @@ struct BatchRef {
     uint32_t n_scans;
     uint32_t n_blocks;
     const ScanRec* __restrict__ s;
+    // per scan: the column height H of its ray tiles (ray_tile.h; k_tile_detect), 0 for a scan
+    // whose blocks are consecutive rays; null: no scan of the batch has tiles
+    const uint32_t* __restrict__ tile;
 };
 
 struct Table {
@@ -267,7 +271,9 @@ struct Counters {
 constexpr uint32_t METRIC_RING = 256;
 struct BatchRecord {
     uint32_t batch_id, n_active, n_new, ovf;
-    uint32_t committed, pool_count, pad[2];
+    uint32_t committed, pool_count;
+    uint32_t tiled;  // scans of the batch walked as ray tiles (ray_tile.h)
+    uint32_t pad;
     unsigned long long rays, pairs, vox, dirty;
 };
 
@@ -322,6 +328,10 @@ struct KernelTimer {
 hipError_t launch_count(const float* d_xyz, const BatchRef& D, const RayConst& R, const Table& T,
                         const Work& Wk, Globals* G, int parity, hipStream_t st, const KTime& kt = {},
                         bool wide = false, bool paired = false);
+// Ray tiles (ray_tile.h): tile[t] = scan t's column height when its points are intact columns
+// (read at the column boundaries), else 0; force != 0: tile[t] = force for every scan
+hipError_t launch_tile_detect(const float* d_xyz, const BatchRef& D, uint32_t* tile,
+                              uint32_t force, hipStream_t st);
 // table chunks of k_compact (Work::cagg holds two uint4 per chunk)
 #ifndef TSDF_CMP_CHUNK
 #define TSDF_CMP_CHUNK 1024
@@ -343,7 +353,8 @@ hipError_t launch_spans(const BatchRef& D, const RayConst& R, const Table& T, co
                         Globals* G, int parity, int nstep, hipStream_t st);
 hipError_t launch_place(const float* d_xyz, const BatchRef& D, const RayConst& R, const Table& T,
                         const Work& Wk, Globals* G, int parity, hipStream_t st, const KTime& kt = {});
-hipError_t launch_finish(Globals* G, int parity, uint32_t batch_id, hipStream_t st);
+hipError_t launch_finish(Globals* G, int parity, uint32_t batch_id, const BatchRef& D,
+                         hipStream_t st);
 // bytes (a multiple of 16) from device-accessible pinned host memory to device memory, then
 // *done = seq (done: device address of a pinned host word)
 hipError_t launch_upload(const void* host_src, void* dst, uint32_t bytes,

@@ -1,7 +1,8 @@
 // tsdf_kernels.hip — gfx950 kernels of the TSDF integration hot path (MAP_BACKEND_IDX = 4).
 //
 // One launch sequence integrates a BATCH of up to MAX_BATCH consecutive scans:
-//   k_count     one workgroup per 1024 consecutive rays of one scan: every lane walks its rays' DDA
+//   k_count     one workgroup per block of 1024 rays of one scan (consecutive rays, or a 32 x 32
+//               tile of a column-regular scan: ray_tile.h): every lane walks its rays' DDA
 //               over the truncation band; each distinct brick a ray updates goes into the
 //               workgroup's LDS hash (one LDS CAS + one LDS atomicAdd per (ray, brick) pair, which
 //               also gives the pair its rank).  Then one lane per distinct brick finds-or-inserts it
@@ -145,8 +146,12 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? F64
 #endif
     // block g of the workgroup is G bx + g (past the batch's last block: an empty range)
     uint32_t tb[G], r0b[G], r1b[G];
+    TileBlock tlb[G];  // which rays the block's slots are (ray_tile.h)
 #pragma unroll
-    for (int g = 0; g < G; g++) block_range(D, G * bx + g, tb[g], r0b[g], r1b[g]);
+    for (int g = 0; g < G; g++) {
+        block_range(D, G * bx + g, tb[g], r0b[g], r1b[g]);
+        tlb[g] = block_tile(D, G * bx + g, tb[g]);
+    }
     const bool split = G == 2 && tb[G - 1] != tb[0];
     for (int j = threadIdx.x; j < HCAP; j += NT) {
         s_key[j] = EMPTY_KEY;
@@ -159,7 +164,7 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? F64
     uint32_t valid = 0, npairs = 0;
     // The pair code of (ray, brick run): LDS-hash rank in the workgroup's run for the brick, or a
     // fallback record when the LDS hash is full.  cnt_in = the pair's gated voxels (<= MAX_IN_BRICK).
-    // A run's samples are counted per (block, half) -- rays [0, RPB/2) and [RPB/2, RPB) of the
+    // A run's samples are counted per (block, half) -- slots [0, RPB/2) and [RPB/2, RPB) of the
     // block: k_place runs one 512-lane workgroup per half -- as 16-bit fields of s_cnt, field
     // sub = 2 g + half (a field holds at most RPB/2 * MAX_IN_BRICK samples); the pair's rank is
     // within its sub-run.
@@ -184,8 +189,9 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? F64
         Wk.fb[f] = make_uint4(h, t, rk, 0u);
         return PAIR_FB | (cnt_in << PAIR_CNT_SHIFT) | f;
     };
-    // G = 1: the lanes stride the block's rays; G = 2: pass q covers rays [q NT, (q + 1) NT) of
-    // the workgroup's 2 RPB, so the block (and its scan) is uniform in a pass
+    // G = 1: the lanes stride the block's slots; G = 2: pass q covers slots [q NT, (q + 1) NT) of
+    // the workgroup's 2 RPB, so the block (and its scan) is uniform in a pass.  Slot sl of the
+    // block is ray i of the batch (tile_point: consecutive rays, or a 32 x 32 tile of the scan)
     constexpr int PASSES = G == 1 ? 1 : G * RPB / NT;
 #pragma unroll 1
     for (int pass = 0; pass < PASSES; pass++) {
@@ -195,16 +201,19 @@ __global__ __launch_bounds__(NT, SEM == 2 && (NT == CNT_THREADS || G == 2) ? F64
         const uint32_t r1 = g ? r1b[G - 1] : r1b[0];
         const float ox = D.s[t].ox, oy = D.s[t].oy, oz = D.s[t].oz;
         const float* __restrict__ xs = scan_xyz(xyz, D, t, R);
-        const uint32_t lo = G == 1 ? r0 + threadIdx.x : r0 + (uint32_t)(pass * NT) % RPB + threadIdx.x;
-        const uint32_t hi = G == 1 ? r1 : min(r1, r0 + (uint32_t)(pass * NT) % RPB + NT);
-        for (uint32_t i = lo; i < hi; i += NT) {
+        const TileBlock tl = g ? tlb[G - 1] : tlb[0];
+        const uint32_t ray0 = D.s[t].off, nsl = r1 > r0 ? r1 - r0 : 0u;  // the block's slots
+        const uint32_t lo = G == 1 ? threadIdx.x : (uint32_t)(pass * NT) % RPB + threadIdx.x;
+        const uint32_t hi = G == 1 ? nsl : min(nsl, (uint32_t)(pass * NT) % RPB + NT);
+        for (uint32_t sl = lo; sl < hi; sl += NT) {
+            const uint32_t i = ray0 + tile_point(tl, sl);
             uint32_t* pc = Wk.pair + (size_t)i * maxp;
             uint32_t k = 0;
             typename Walk<SEM>::State r;
             const bool ok = Walk<SEM>::init(R, D, t, i, xs[3 * (size_t)i], xs[3 * (size_t)i + 1],
                                             xs[3 * (size_t)i + 2], r);
             valid += ok ? 1u : 0u;
-            const uint32_t sub = 2u * (uint32_t)g + (i - r0 >= (uint32_t)(RPB / 2) ? 1u : 0u);
+            const uint32_t sub = 2u * (uint32_t)g + (sl >= (uint32_t)(RPB / 2) ? 1u : 0u);
             // One pair per distinct brick; a line visits a brick in one contiguous run of DDA
             // voxels, so a pair closes when the next gated voxel's brick differs.
             if (maxp <= 4) {
@@ -544,6 +553,46 @@ hipError_t launch_sector_flags(const float* d_xyz, const BatchRef& D, const RayC
     const uint32_t per = FLG_THREADS / 64;
     k_sector_flags<<<(D.n_blocks + per - 1) / per, FLG_THREADS, 0, st>>>(d_xyz, D, R, Wk, G,
                                                                         parity);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_tile_detect: one workgroup per scan decides whether the scan's blocks are ray tiles
+// (ray_tile.h: the column height H when the points are intact H-beam columns, else 0).  It reads
+// the points at the column boundaries only -- six per column, ~72 KB of a 128 x 1024 scan, in a
+// few dependent round trips (64 workgroups for a 64-scan batch: latency, not bandwidth) -- and
+// needs nothing of the previous batch, so the host launches it ahead of the batch's cross-batch
+// wait.  tile_detect (ray_tile.h) is the same decision, serial.
+constexpr int TDT_THREADS = 1024;  // a 1024-column scan's boundaries in one pass
+__global__ __launch_bounds__(TDT_THREADS) void k_tile_detect(const float* __restrict__ xyz,
+                                                            BatchRef D, uint32_t* __restrict__ tile,
+                                                            uint32_t force) {
+    const uint32_t t = blockIdx.x;
+    if (force) {
+        if (threadIdx.x == 0) tile[t] = force;
+        return;
+    }
+    const uint32_t n = D.s[t + 1].off - D.s[t].off;
+    const float* __restrict__ xs = xyz + 3 * ((size_t)D.s[t].off + D.s[t].xoff);
+    const float ox = D.s[t].ox, oy = D.s[t].oy, oz = D.s[t].oz;
+    uint32_t found = 0;
+    for (uint32_t H = 64; H <= 256 && !found; H *= 2) {  // uniform
+        if (!tile_shape_ok(n, H)) continue;
+        const float dir = tile_direction(xs, H, ox, oy, oz);
+        // boundary 1 by every lane first (uniform): a scan of taller columns leaves here, without
+        // the pass over its boundaries
+        bool ok = dir != 0.0f && tile_boundary_ok(xs, H, 1, ox, oy, oz, dir);
+        if (ok)
+            for (uint32_t c = 2 + threadIdx.x; ok && c < n / H; c += TDT_THREADS)
+                ok = tile_boundary_ok(xs, H, c, ox, oy, oz, dir);
+        if (__syncthreads_and(ok)) found = H;
+    }
+    if (threadIdx.x == 0) tile[t] = found;
+}
+
+hipError_t launch_tile_detect(const float* d_xyz, const BatchRef& D, uint32_t* tile,
+                              uint32_t force, hipStream_t st) {
+    k_tile_detect<<<D.n_scans, TDT_THREADS, 0, st>>>(d_xyz, D, tile, force);
     return hipGetLastError();
 }
 
@@ -942,17 +991,19 @@ __global__ __launch_bounds__(PLC_THREADS, SEM == 2 ? F64_PLACE_WAVES : 1) void k
     }
     uint32_t t, r0, r1;
     block_range(D, wb >> 1, t, r0, r1);
-    r0 += (wb & 1u) * PLC_THREADS;
+    // the lane's slot of the block and its ray (ray_tile.h: k_count's map)
+    const uint32_t sl = (wb & 1u) * PLC_THREADS + threadIdx.x;
+    const bool has_ray = r0 + sl < r1;
+    const uint32_t i = D.s[t].off + tile_point(block_tile(D, wb >> 1, t), sl);
     const uint4* bt = Wk.blk + (size_t)wb * HCAP;
     const uint32_t maxp = Wk.maxp;
-    const uint32_t i = r0 + threadIdx.x;
     // Every independent global load is issued first, so the prologue waits two memory round trips
     // (list entry -> its cell) instead of four (point -> pair codes, list -> cell): the ray's point
     // and pair codes, the list length, and each lane's first list entry.
     float px = 0.0f, py = 0.0f, pz = 0.0f;
     uint4 code4 = make_uint4(NO_PAIR, NO_PAIR, NO_PAIR, NO_PAIR);
     const uint32_t* pc = Wk.pair + (size_t)i * maxp;
-    if (i < r1) {
+    if (has_ray) {
         const float* __restrict__ xs = scan_xyz(xyz, D, t, R);
         px = xs[3 * (size_t)i];
         py = xs[3 * (size_t)i + 1];
@@ -978,7 +1029,7 @@ __global__ __launch_bounds__(PLC_THREADS, SEM == 2 ? F64_PLACE_WAVES : 1) void k
                                : NO_PAIR;
     const float ox = D.s[t].ox, oy = D.s[t].oy, oz = D.s[t].oz;
     typename Walk<SEM>::State r;
-    const bool ok = i < r1 && Walk<SEM>::init(R, D, t, i, px, py, pz, r);
+    const bool ok = has_ray && Walk<SEM>::init(R, D, t, i, px, py, pz, r);
     // sector sharding: a half block without a ray of this GPU's sector has no samples to place
     if (R.sec_on && !block_any<PLC_THREADS>(ok, s_vote[0])) return;
     if constexpr (SEM == 3) s_w0[threadIdx.x] = ok ? r.w0 : 0.0f;
@@ -1351,10 +1402,16 @@ hipError_t launch_place(const float* d_xyz, const BatchRef& D, const RayConst& R
 // ordered after every reader of this batch).  A batch that raised an overflow marks the context
 // failed (its id kept for the host's replay); with G->retry, it and every later batch until the
 // host's check do not commit.
-__global__ void k_finish(Globals* G, int parity, uint32_t batch_id) {
+__global__ void k_finish(Globals* G, int parity, uint32_t batch_id,
+                         const uint32_t* __restrict__ tile, uint32_t n_scans) {
     constexpr int NW = sizeof(Counters) / 4;
     Counters* C = &G->ctr[parity];
     const uint32_t ovf = C->ovf, failed = G->failed;
+    // the batch's scans walked as ray tiles (the metrics record; one wave)
+    uint32_t tiled = 0;
+    if (tile)
+        for (uint32_t j = threadIdx.x; j < n_scans; j += 64) tiled += tile[j] ? 1u : 0u;
+    tiled = wave_sum<uint32_t>(tiled);
     const bool commit = !(G->retry && (ovf || failed));
     __syncthreads();  // every lane read the flags before lane 0 updates them
     if (threadIdx.x < 8 && commit) {
@@ -1379,7 +1436,8 @@ __global__ void k_finish(Globals* G, int parity, uint32_t batch_id) {
         r.ovf = ovf;
         r.committed = commit ? 1u : 0u;
         r.pool_count = G->pool_count;
-        r.pad[0] = r.pad[1] = 0u;
+        r.tiled = tiled;
+        r.pad = 0u;
         r.rays = r.pairs = r.vox = r.dirty = 0ull;
         for (int k = 0; k < 8; k++) {
             r.rays += C->n_rays[k];
@@ -1418,8 +1476,9 @@ hipError_t launch_upload(const void* host_src, void* dst, uint32_t bytes,
     return hipGetLastError();
 }
 
-hipError_t launch_finish(Globals* G, int parity, uint32_t batch_id, hipStream_t st) {
-    k_finish<<<1, 64, 0, st>>>(G, parity, batch_id);
+hipError_t launch_finish(Globals* G, int parity, uint32_t batch_id, const BatchRef& D,
+                         hipStream_t st) {
+    k_finish<<<1, 64, 0, st>>>(G, parity, batch_id, D.tile, D.n_scans);
     return hipGetLastError();
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ray_tile.h"
 #include "tsdf_device.h"
 
 namespace tsdf {
@@ -221,6 +222,14 @@ __device__ __forceinline__ void block_range(const BatchRef& D, uint32_t b, uint3
     t = lo;
     r0 = D.s[t].off + (b - D.s[t].blk) * RPB;
     r1 = min(D.s[t + 1].off, r0 + RPB);
+}
+
+// Block b of scan t as a ray tile (ray_tile.h): slot s of the block is batch ray
+// D.s[t].off + tile_point(., s); r1 - r0 of block_range is the block's slot count either way.
+static_assert(RPB == (int)TILE_RAYS, "ray_tile.h maps blocks of RPB slots");
+__device__ __forceinline__ TileBlock block_tile(const BatchRef& D, uint32_t b, uint32_t t) {
+    const uint32_t H = D.tile ? D.tile[t] : 0u;
+    return tile_block(D.s[t + 1].off - D.s[t].off, H, b - D.s[t].blk);
 }
 
 // The points of scan t for its batch rays i (ABI v10): xyz[3 (i + xoff)], xoff nonzero only for
