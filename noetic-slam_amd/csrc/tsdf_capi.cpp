@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/tsdf_hip.h"
+#include "../../include/tsdf_hip_prune.h"
 #include "../../include/tsdf_hip_raycast.h"
 #include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
@@ -35,6 +36,7 @@
 #include "ctx_plan.h"
 #include "host_pack.h"
 #include "pack_pool.h"
+#include "prune_plan.h"
 #include "tsdf_device.h"
 
 using namespace tsdf;
@@ -2467,6 +2469,185 @@ int tsdf_import_bricks(tsdf_ctx* c, const int32_t* coords, const float* sdf, con
     HIPCHK(c, launch_import(c->T, c->Pl, dc, (uint32_t)n, ds, dw, dt, c->G, merge_cap(c), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return tsdf_sync(c);
+}
+
+}  // extern "C"
+
+// ---- removing bricks (include/tsdf_hip_prune.h; kernels in tsdf_prune.hip) --------
+
+// One removal over the pool's n slots: the keep flags, their prefix and the lists it gives
+// (launch_rm_scan), all in the call's scratch.
+struct Removal {
+    uint32_t n = 0;                        // pool slots before
+    uint32_t new_count = 0, n_moves = 0;   // kept bricks; kept bricks that change slot
+    uint32_t *keep = nullptr, *bsum = nullptr, *boff = nullptr, *res = nullptr, *rml = nullptr,
+             *mover = nullptr;
+    uint32_t removed() const { return n - new_count; }
+};
+
+static int removal_alloc(tsdf_ctx* c, Scratch& tmp, uint32_t n, Removal& M) {
+    M.n = n;
+    HIPCHK(c, tmp.get(c, &M.keep, n));
+    HIPCHK(c, tmp.get(c, &M.bsum, rm_scan_blocks(n)));
+    HIPCHK(c, tmp.get(c, &M.boff, rm_scan_blocks(n)));
+    HIPCHK(c, tmp.get(c, &M.res, 2));
+    HIPCHK(c, tmp.get(c, &M.rml, n));
+    HIPCHK(c, tmp.get(c, &M.mover, n));
+    return TSDF_OK;
+}
+
+// keep is written: rank the slots and read the counts back
+static int removal_rank(tsdf_ctx* c, Removal& M) {
+    uint32_t res[2] = {0u, 0u};
+    HIPCHK(c, launch_rm_scan(M.keep, M.n, M.bsum, M.boff, M.res, M.rml, M.mover, c->stream));
+    HIPCHK(c, hipMemcpyAsync(res, M.res, sizeof res, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    M.new_count = res[0];
+    M.n_moves = res[1];
+    if (M.new_count > M.n || M.n_moves > std::min(M.new_count, M.removed()))
+        return fail(c, TSDF_EHIP, "removal: inconsistent ranks (%u of %u kept, %u moves)",
+                    M.new_count, M.n, M.n_moves);
+    return TSDF_OK;
+}
+
+// Fill the holes from the pool's tail and leave the context as the integrate path expects it.
+// Nothing removed: nothing is touched.
+static int removal_compact(tsdf_ctx* c, const Removal& M) {
+    if (!M.removed()) return TSDF_OK;
+    const Capacity& K = c->K;
+    const uint64_t at = (uint64_t)M.new_count * BRICK_VOX, freed = (uint64_t)M.removed() * BRICK_VOX;
+    HIPCHK(c, launch_rm_move(c->T, c->Pl, M.rml, M.mover, M.n_moves, c->stream));
+    // fresh slots hold the background: tsdf_create fills the pool once and allocation (k_compact,
+    // k_import_insert) hands slots out without touching their voxels
+    HIPCHK(c, launch_fill(c->Pl.sdf + at, c->R.bg, freed, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->Pl.weight + at, 0, freed * sizeof(float), c->stream));
+    // the table again from the slot -> key map, as after a capacity growth
+    HIPCHK(c, launch_fill_u64(K.keys, EMPTY_KEY, K.cap, c->stream));
+    HIPCHK(c, launch_fill_u32(K.slots, UNASSIGNED, K.cap, c->stream));
+    // touched and cell[2] are indexed by table entry, and the entries move with the rebuild.
+    // Between batches both are zero on the ordinary path: k_compact_write clears every touched
+    // flag it lists (compact_list, clear = true), and k_integrate / k_integrate_small zero the
+    // whole cell row of every brick of the batch's active list, committed or not.  What that
+    // leaves out is a batch that overflowed a capacity that could not grow (a brick beyond the
+    // active list or without a pool slot keeps its row, and TSDF_ENOMEM says that updates were
+    // dropped).  A stale row under a moved entry would then corrupt another brick's sample
+    // positions, so both arrays are cleared here as alloc_capacity leaves them, instead of relying
+    // on every overflow path.
+    const size_t cells = K.cap * c->plan.cell_stride *
+                         (c->plan.fused ? sizeof(uint64_t) : sizeof(uint32_t));
+    HIPCHK(c, hipMemsetAsync(K.touched, 0, K.cap * sizeof(uint32_t), c->stream));
+    for (int q = 0; q < 2; q++) HIPCHK(c, hipMemsetAsync(K.cell[q], 0, cells, c->stream));
+    HIPCHK(c, launch_rehash(c->T, M.new_count, c->G, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&c->G->pool_count, &M.new_count, 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TSDF_OK;
+}
+
+// The entry checks the three calls share (those of tsdf_import_bricks) and the drained brick count
+static int removal_enter(tsdf_ctx* c, const int32_t* lo, const int32_t* hi, bool box, uint64_t* nb) {
+    if (border_busy(c)) return TSDF_EINVAL;
+    if (box) {
+        if (!lo || !hi) return fail(c, TSDF_EINVAL, "null box");
+        for (int a = 0; a < 3; a++)
+            if (lo[a] > hi[a]) return fail(c, TSDF_EINVAL, "box: lo > hi");
+    }
+    return pool_bricks(c, nb);
+}
+
+extern "C" {
+
+int tsdf_prune(tsdf_ctx* c, float min_weight, uint64_t* n_removed) {
+    if (!c) return TSDF_EINVAL;
+    if (!(min_weight >= 0.0f)) return fail(c, TSDF_EINVAL, "prune: min_weight is negative or NaN");
+    uint64_t nb = 0;
+    int rc = removal_enter(c, nullptr, nullptr, false, &nb);
+    if (rc) return rc;
+    if (n_removed) *n_removed = 0;
+    if (!nb) return TSDF_OK;
+    Scratch tmp;
+    Removal M;
+    rc = removal_alloc(c, tmp, (uint32_t)nb, M);
+    if (rc) return rc;
+    HIPCHK(c, launch_rm_flag_prune(c->Pl, M.n, min_weight, c->R.bg, M.keep, c->stream));
+    rc = removal_rank(c, M);
+    if (rc) return rc;
+    if (n_removed) *n_removed = M.removed();
+    return removal_compact(c, M);
+}
+
+int tsdf_count_outside(tsdf_ctx* c, const int32_t lo[3], const int32_t hi[3], uint64_t* n) {
+    if (!c || !n) return TSDF_EINVAL;
+    uint64_t nb = 0;
+    int rc = removal_enter(c, lo, hi, true, &nb);
+    if (rc) return rc;
+    *n = 0;
+    if (!nb) return TSDF_OK;
+    Scratch tmp;
+    Removal M;
+    rc = removal_alloc(c, tmp, (uint32_t)nb, M);
+    if (rc) return rc;
+    HIPCHK(c, launch_rm_flag_box(c->T, M.n, lo, hi, M.keep, c->stream));
+    rc = removal_rank(c, M);
+    if (rc) return rc;
+    *n = M.removed();
+    return TSDF_OK;
+}
+
+int tsdf_evict_outside(tsdf_ctx* c, const int32_t lo[3], const int32_t hi[3], int32_t* coords,
+                       float* sdf, float* weight, uint64_t cap, uint64_t* n_out) {
+    if (!c) return TSDF_EINVAL;
+    uint64_t nb = 0;
+    int rc = removal_enter(c, lo, hi, true, &nb);
+    if (rc) return rc;
+    if (n_out) *n_out = 0;
+    if (!nb) return TSDF_OK;
+    Scratch tmp;
+    Removal M;
+    rc = removal_alloc(c, tmp, (uint32_t)nb, M);
+    if (rc) return rc;
+    HIPCHK(c, launch_rm_flag_box(c->T, M.n, lo, hi, M.keep, c->stream));
+    rc = removal_rank(c, M);
+    if (rc) return rc;
+    const uint64_t count = M.removed();
+    if (n_out) *n_out = count;
+    const bool want = coords || sdf || weight;
+    if (want && count > cap)
+        return fail(c, TSDF_EOVERFLOW, "evict needs %llu bricks", (unsigned long long)count);
+    if (!count) return TSDF_OK;
+    if (want) {  // the copy-out, before anything moves
+        std::vector<uint64_t> keys(nb);
+        std::vector<uint32_t> slots(count);
+        HIPCHK(c, hipMemcpy(keys.data(), c->T.brick_keys, nb * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(slots.data(), M.rml, count * 4, hipMemcpyDeviceToHost));
+        for (uint32_t s : slots)
+            if (s >= nb) return fail(c, TSDF_EHIP, "removal: slot %u out of range", s);
+        std::sort(slots.begin(), slots.end(),
+                  [&](uint32_t a, uint32_t b) { return brick_key_less_zyx(keys[a], keys[b]); });
+        if (coords)
+            for (uint64_t i = 0; i < count; i++)
+                for (int a = 0; a < 3; a++) coords[3 * i + a] = brick_key_coord(keys[slots[i]], a);
+        const int arrays = (sdf ? 1 : 0) + (weight ? 1 : 0);
+        if (arrays) {
+            // the sorted slots take the place of the keep flags (ranked already; count <= n);
+            // the pieces' size: prune_plan.h
+            const uint64_t per = evict_piece_bricks(arrays);
+            uint32_t* d_slots = M.keep;
+            float *ds = nullptr, *dw = nullptr;
+            HIPCHK(c, hipMemcpy(d_slots, slots.data(), count * 4, hipMemcpyHostToDevice));
+            if (sdf) HIPCHK(c, tmp.get(c, &ds, std::min(per, count) * BRICK_VOX));
+            if (weight) HIPCHK(c, tmp.get(c, &dw, std::min(per, count) * BRICK_VOX));
+            for (uint64_t i0 = 0; i0 < count; i0 += per) {
+                const uint64_t m = std::min(per, count - i0);
+                HIPCHK(c, launch_rm_gather(c->Pl, d_slots + i0, (uint32_t)m, ds, dw, c->stream));
+                HIPCHK(c, hipStreamSynchronize(c->stream));
+                if (sdf)
+                    HIPCHK(c, hipMemcpy(sdf + i0 * BRICK_VOX, ds, m * BRICK_VOX * 4, hipMemcpyDeviceToHost));
+                if (weight)
+                    HIPCHK(c, hipMemcpy(weight + i0 * BRICK_VOX, dw, m * BRICK_VOX * 4, hipMemcpyDeviceToHost));
+            }
+        }
+    }
+    return removal_compact(c, M);
 }
 
 int tsdf_get_stats(tsdf_ctx* c, tsdf_stats* out) {

@@ -486,5 +486,27 @@ hipError_t launch_raycast(const Table& T, const Pool& Pl, const RayConst& R, con
                           uint8_t* d_hit, hipStream_t st);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, uint64_t n, hipStream_t st);
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, uint64_t n, hipStream_t st);
+// removing bricks (tsdf_prune.hip; include/tsdf_hip_prune.h), over the pool slots [0, n)
+constexpr uint32_t RM_BLOCK = 256;        // slots per block of the keep scan (one lane each)
+constexpr int RM_SCAN_THREADS = 64;       // block sums the scan's middle phase takes per round
+inline uint32_t rm_scan_blocks(uint64_t n) { return (uint32_t)((n + RM_BLOCK - 1) / RM_BLOCK); }
+// keep[slot] = 1 when the brick's coordinates lie in lo <= b < hi on every axis
+hipError_t launch_rm_flag_box(const Table& T, uint32_t n, const int32_t lo[3], const int32_t hi[3],
+                              uint32_t* d_keep, hipStream_t st);
+// voxels with W < min_w reset to (bg, 0); keep[slot] = 1 when an observed voxel is left
+hipError_t launch_rm_flag_prune(const Pool& Pl, uint32_t n, float min_w, float bg, uint32_t* d_keep,
+                                hipStream_t st);
+// the prefix of keep: d_res[0] = new_count (kept bricks), d_res[1] = moves; d_rml[0, n - new_count)
+// the removed slots in slot order, of which the first d_res[1] are the holes below new_count;
+// d_mover[0, d_res[1]) the kept slots at or above new_count.  d_bsum / d_boff: rm_scan_blocks(n)
+// words each; d_rml / d_mover: n words each
+hipError_t launch_rm_scan(const uint32_t* d_keep, uint32_t n, uint32_t* d_bsum, uint32_t* d_boff,
+                          uint32_t* d_res, uint32_t* d_rml, uint32_t* d_mover, hipStream_t st);
+// bricks d_slots[0, m) -> rows [0, m) of d_sdf / d_w (either may be null)
+hipError_t launch_rm_gather(const Pool& Pl, const uint32_t* d_slots, uint32_t m, float* d_sdf,
+                            float* d_w, hipStream_t st);
+// brick d_mover[i] -> slot d_hole[i] (voxels and the slot's key), i < n_moves
+hipError_t launch_rm_move(const Table& T, const Pool& Pl, const uint32_t* d_hole,
+                          const uint32_t* d_mover, uint32_t n_moves, hipStream_t st);
 
 }  // namespace tsdf

@@ -798,7 +798,8 @@ __device__ __forceinline__ uint64_t mix64(uint64_t k) {
 }
 
 // Find-or-insert a brick key; returns the table index or -1 when the table is full.  Keys are
-// never removed, so a stale EMPTY read is resolved by the CAS and a non-EMPTY read is final.
+// never removed while a kernel inserts (prune and evict rebuild the whole table between batches,
+// tsdf_prune.hip), so a stale EMPTY read is resolved by the CAS and a non-EMPTY read is final.
 __device__ __forceinline__ int64_t table_insert(const Table& T, uint64_t key, uint32_t* overflow) {
     uint64_t h = mix64(key) & T.mask;
     for (uint64_t probe = 0; probe <= T.mask; probe++) {

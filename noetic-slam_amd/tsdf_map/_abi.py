@@ -195,6 +195,16 @@ RAYCAST_SIGNATURES = {
                                C.c_int32, C.c_float, FP, FP, U8P]),
 }
 
+# include/tsdf_hip_prune.h (TSDF_PRUNE_API): removing bricks (prune, evict), likewise a feature of
+# libtsdf_hip.so outside the contract, declared on the HIP library only.
+PRUNE_SIGNATURES = {
+    "tsdf_prune": (C.c_int, [P, C.c_float, U64P]),
+    "tsdf_count_outside": (C.c_int, [P, I3, I3, U64P]),
+    "tsdf_evict_outside": (C.c_int, [P, I3, I3, I3, FP, FP, C.c_uint64, U64P]),
+}
+BRICK_COORD_MIN = -(1 << 20)  # the packable brick coordinates: MIN <= b < MAX (brick_key.h)
+BRICK_COORD_MAX = 1 << 20
+
 
 def declare(lib, names=None, optional=(), table=None):
     """Attach restype/argtypes for the ABI symbols present in `lib`; raise if a required one is

@@ -36,6 +36,8 @@ def load_hip_library(path=None):
     _abi.declare(lib, table=_abi.SAMPLE_SIGNATURES)
     # ... and the raycast (include/tsdf_hip_raycast.h)
     _abi.declare(lib, table=_abi.RAYCAST_SIGNATURES)
+    # ... and removing bricks (include/tsdf_hip_prune.h)
+    _abi.declare(lib, table=_abi.PRUNE_SIGNATURES)
     if lib.tsdf_abi_version() != ABI_VERSION:
         raise RuntimeError("libtsdf_hip.so ABI version mismatch")
     if path is None:

@@ -400,6 +400,70 @@ class TSDFVolume:
         """Every voxel with weight > 0: (ijk (n,3) int32, sdf (n,), weight (n,)), sorted (z,y,x)."""
         return bricks_to_voxels(*self.export_bricks())
 
+    # -- removing bricks (include/tsdf_hip_prune.h) ---------------------------------------------
+    def _prune_fn(self, name):
+        """An entry point of include/tsdf_hip_prune.h, detected by the symbol like `_sample_fn`."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (prune and evict are part of "
+                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    @staticmethod
+    def _box(lo, hi):
+        lo = np.ascontiguousarray(np.asarray(lo, np.int64).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(hi, np.int64).reshape(3))
+        if np.any(lo > hi):
+            raise ValueError("lo > hi")
+        # (bricks beyond the packable range do not exist: clamping changes no answer)
+        lo = np.clip(lo, _abi.BRICK_COORD_MIN, _abi.BRICK_COORD_MAX).astype(np.int32)
+        hi = np.clip(hi, _abi.BRICK_COORD_MIN, _abi.BRICK_COORD_MAX).astype(np.int32)
+        return lo, hi
+
+    def prune(self, min_weight):
+        """VDBVolume.prune: every voxel with weight < min_weight goes back to the background, and
+        every brick left without an observed voxel is removed, in place.  Returns the number of
+        bricks removed."""
+        fn = self._prune_fn("tsdf_prune")
+        n = C.c_uint64()
+        self._check(fn(self._ctx, float(min_weight), C.byref(n)), "prune")
+        return n.value
+
+    def count_outside(self, lo, hi):
+        """The bricks whose brick coordinate (voxel // 8) is not in lo <= b < hi on every axis."""
+        fn = self._prune_fn("tsdf_count_outside")
+        lo, hi = self._box(lo, hi)
+        n = C.c_uint64()
+        self._check(fn(self._ctx, lo.ctypes.data_as(_abi.I3), hi.ctypes.data_as(_abi.I3),
+                       C.byref(n)), "count_outside")
+        return n.value
+
+    def evict_outside(self, lo, hi, copy_out=True):
+        """Remove the bricks outside the brick box lo <= b < hi.  copy_out: return them as
+        `export_bricks` would, (coords, sdf, weight) sorted by brick (z, y, x) -- `import_bricks`
+        takes them back; otherwise return their number."""
+        fn = self._prune_fn("tsdf_evict_outside")
+        blo, bhi = self._box(lo, hi)
+        plo, phi = blo.ctypes.data_as(_abi.I3), bhi.ctypes.data_as(_abi.I3)
+        n_out = C.c_uint64()
+        if not copy_out:
+            self._check(fn(self._ctx, plo, phi, None, None, None, 0, C.byref(n_out)),
+                        "evict_outside")
+            return n_out.value
+        for _ in range(2):
+            nb = self.count_outside(blo, bhi)
+            coords = np.empty((nb, 3), np.int32)
+            s = np.empty((nb, 8, 8, 8), np.float32)
+            w = np.empty_like(s)
+            rc = fn(self._ctx, plo, phi, coords.ctypes.data_as(_abi.I3),
+                    s.ctypes.data_as(_abi.FP), w.ctypes.data_as(_abi.FP), nb, C.byref(n_out))
+            if rc == _abi.TSDF_EOVERFLOW:
+                continue
+            self._check(rc, "evict_outside")
+            k = n_out.value
+            return coords[:k], s[:k], w[:k]
+        raise TsdfError(_abi.TSDF_EOVERFLOW, "evict_outside: brick count kept changing")
+
     def save(self, path):
         """Checkpoint: the brick map as .npz (keys, sdf, weight, parameters)."""
         c, s, w = self.export_bricks()
