@@ -28,12 +28,14 @@
 #include <vector>
 
 #include "../../include/tsdf_hip.h"
+#include "../../include/tsdf_hip_esdf.h"
 #include "../../include/tsdf_hip_prune.h"
 #include "../../include/tsdf_hip_raycast.h"
 #include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
 #include "brick_key.h"
 #include "ctx_plan.h"
+#include "esdf_plan.h"
 #include "host_pack.h"
 #include "pack_pool.h"
 #include "prune_plan.h"
@@ -2182,6 +2184,80 @@ int tsdf_raycast(tsdf_ctx* c, const float* org, const float* dir, uint64_t n, co
         if (normal) HIPCHK(c, hipMemcpy(normal + 3 * i0, dn, m * 12, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(hit + i0, dh, m, hipMemcpyDeviceToHost));
     }
+    return TSDF_OK;
+}
+
+// ---- distance field of a box (include/tsdf_hip_esdf.h) ------------------------------------------
+
+// The rules both entry points share (the output buffers apart), reported in the header's order; B:
+// the box's extents.
+static int esdf_args(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], uint32_t radius_vox,
+                     float site_band, float min_weight, EsdfBox* B) {
+    if (!lo || !hi) return fail(c, TSDF_EINVAL, "esdf: null argument");
+    const int a = esdf_check(lo, hi, radius_vox, site_band, min_weight, B);
+    // (min_weight is map_query_args' own rule and text)
+    return map_query_args(c, "esdf", "a distance field of", TSDF_SAMPLE_NEAREST, min_weight,
+                          a == ESDF_ARG_WEIGHT ? nullptr : esdf_arg_text(a));
+}
+
+// The field of box B into device buffers; the scratch lives for the call.
+static int esdf_run(tsdf_ctx* c, const int64_t lo[3], const EsdfBox& B, uint32_t radius_vox,
+                    float site_band, float min_weight, float* d_dist, uint8_t* d_flags) {
+    // one allocation: two u16 planes and the class bytes, each part 16-byte aligned
+    const size_t plane = (size_t)((2 * B.total + 15) & ~(uint64_t)15);
+    Scratch tmp;
+    uint8_t* s = nullptr;
+    if (tmp.get(c, &s, 2 * plane + (size_t)B.total) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, TSDF_ENOMEM, "esdf: scratch allocation of %llu bytes failed",
+                    (unsigned long long)esdf_scratch_bytes(B.total));
+    }
+    uint16_t *g0 = reinterpret_cast<uint16_t*>(s), *g1 = reinterpret_cast<uint16_t*>(s + plane);
+    uint8_t* cls = s + 2 * plane;
+    HIPCHK(c, launch_esdf(c->T, c->Pl, lo, B.n, radius_vox, site_band, min_weight, c->R.bg, c->R.vs,
+                          g0, g1, cls, d_dist, d_flags, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TSDF_OK;
+}
+
+int tsdf_esdf_dense_device(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3],
+                           uint32_t radius_vox, float site_band, float min_weight, float* d_dist,
+                           uint8_t* d_flags) {
+    if (!c) return TSDF_EINVAL;
+    EsdfBox B;
+    int rc = esdf_args(c, lo, hi, radius_vox, site_band, min_weight, &B);
+    if (rc) return rc;
+    if (!B.total) return TSDF_OK;
+    if (!d_dist) return fail(c, TSDF_EINVAL, "esdf: null buffer");
+    rc = drain(c);
+    if (rc) return rc;
+    return esdf_run(c, lo, B, radius_vox, site_band, min_weight, d_dist, d_flags);
+}
+
+int tsdf_esdf_dense(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], uint32_t radius_vox,
+                    float site_band, float min_weight, float* dist, uint8_t* flags) {
+    if (!c) return TSDF_EINVAL;
+    EsdfBox B;
+    int rc = esdf_args(c, lo, hi, radius_vox, site_band, min_weight, &B);
+    if (rc) return rc;
+    if (!B.total) return TSDF_OK;
+    if (!dist) return fail(c, TSDF_EINVAL, "esdf: null buffer");
+    rc = drain(c);
+    if (rc) return rc;
+    Scratch out;
+    float* dd = nullptr;
+    uint8_t* df = nullptr;
+    hipError_t e = out.get(c, &dd, B.total);
+    if (e == hipSuccess && flags) e = out.get(c, &df, B.total);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, TSDF_ENOMEM, "esdf: output allocation for %llu voxels failed",
+                    (unsigned long long)B.total);
+    }
+    rc = esdf_run(c, lo, B, radius_vox, site_band, min_weight, dd, df);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(dist, dd, B.total * 4, hipMemcpyDeviceToHost));
+    if (flags) HIPCHK(c, hipMemcpy(flags, df, B.total, hipMemcpyDeviceToHost));
     return TSDF_OK;
 }
 

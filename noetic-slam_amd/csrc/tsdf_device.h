@@ -484,6 +484,12 @@ hipError_t launch_raycast(const Table& T, const Pool& Pl, const RayConst& R, con
                           const float* d_dir, uint64_t n, const OsPose* P, float t_min, float step,
                           uint32_t n_k, int mode, float min_w, float* d_depth, float* d_normal,
                           uint8_t* d_hit, hipStream_t st);
+// distance field of a box (tsdf_esdf.hip; include/tsdf_hip_esdf.h): voxels lo..lo + n - 1, radius in
+// voxels; d_g0 / d_g1: n[0] n[1] n[2] u16 each, d_cls as many bytes (esdf_plan.h); d_flags may be null
+hipError_t launch_esdf(const Table& T, const Pool& Pl, const int64_t lo[3], const uint32_t n[3],
+                       uint32_t radius, float band, float min_w, float bg, float vs, uint16_t* d_g0,
+                       uint16_t* d_g1, uint8_t* d_cls, float* d_dist, uint8_t* d_flags,
+                       hipStream_t st);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, uint64_t n, hipStream_t st);
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, uint64_t n, hipStream_t st);
 // removing bricks (tsdf_prune.hip; include/tsdf_hip_prune.h), over the pool slots [0, n)

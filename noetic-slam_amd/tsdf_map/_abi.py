@@ -205,6 +205,17 @@ PRUNE_SIGNATURES = {
 BRICK_COORD_MIN = -(1 << 20)  # the packable brick coordinates: MIN <= b < MAX (brick_key.h)
 BRICK_COORD_MAX = 1 << 20
 
+# include/tsdf_hip_esdf.h (TSDF_ESDF_API): the Euclidean distance field of a map box, likewise a
+# feature of libtsdf_hip.so outside the contract, declared on the HIP library only.
+ESDF_OBSERVED = 1  # TSDF_ESDF_OBSERVED: W > 0 and W >= min_weight
+ESDF_SITE = 2      # TSDF_ESDF_SITE: observed and |S| <= site_band
+ESDF_CAPPED = 4    # TSDF_ESDF_CAPPED: no site of the box within radius_vox
+ESDF_MAX_RADIUS = 128
+ESDF_SIGNATURES = {
+    "tsdf_esdf_dense": (C.c_int, [P, L3, L3, C.c_uint32, C.c_float, C.c_float, FP, U8P]),
+    "tsdf_esdf_dense_device": (C.c_int, [P, L3, L3, C.c_uint32, C.c_float, C.c_float, P, P]),
+}
+
 
 def declare(lib, names=None, optional=(), table=None):
     """Attach restype/argtypes for the ABI symbols present in `lib`; raise if a required one is

@@ -336,6 +336,50 @@ class TSDFVolume:
         del keep
         return depth, normal, hit.astype(bool)
 
+    # -- distance field of a box (include/tsdf_hip_esdf.h) ---------------------------------------
+    def _esdf_fn(self, name):
+        """An entry point of include/tsdf_hip_esdf.h, detected by the symbol like `_sample_fn`."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (the distance field is part of "
+                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    def esdf_radius(self, max_dist):
+        """radius_vox of a distance field exact up to max_dist metres: ceil(max_dist / voxel_size)
+        in double; ValueError outside 1..128 voxels."""
+        r = math.ceil(float(max_dist) / float(self.voxel_size)) if math.isfinite(max_dist) else 0
+        if not 1 <= r <= _abi.ESDF_MAX_RADIUS:
+            raise ValueError("max_dist must span 1..%d voxels (voxel_size %g)"
+                             % (_abi.ESDF_MAX_RADIUS, self.voxel_size))
+        return int(r)
+
+    def _esdf_args(self, lo, hi, max_dist, site_band):
+        lo = np.ascontiguousarray(np.asarray(lo, np.int64).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(hi, np.int64).reshape(3))
+        if np.any(hi < lo):
+            raise ValueError("hi < lo")
+        band = self.voxel_size if site_band is None else site_band
+        return lo, hi, self.esdf_radius(max_dist), float(band)
+
+    def esdf(self, lo, hi, max_dist, site_band=None, min_weight=0.0):
+        """The Euclidean distance field of voxels lo..hi-1: (dist, flags) as [z, y, x] float32 /
+        uint8 arrays.  dist is the distance in metres from the voxel's centre to the centre of the
+        nearest surface voxel (a "site": observed with |sdf| <= site_band, default one voxel) of
+        the box, exact up to max_dist and capped there, negative where the voxel is observed
+        behind the surface.  flags: ESDF_OBSERVED | ESDF_SITE | ESDF_CAPPED of tsdf_map._abi.
+        Only sites inside the box count: pad the box by the radius (`esdf.esdf_around` does) for
+        clearances that are exact at its rim.  include/tsdf_hip_esdf.h states the rules."""
+        lo, hi, radius, band = self._esdf_args(lo, hi, max_dist, site_band)
+        fn = self._esdf_fn("tsdf_esdf_dense")
+        dims = hi - lo
+        dist = np.empty((dims[2], dims[1], dims[0]), np.float32)
+        flags = np.empty(dist.shape, np.uint8)
+        self._check(fn(self._ctx, lo.ctypes.data_as(_abi.L3), hi.ctypes.data_as(_abi.L3), radius,
+                       band, float(min_weight), dist.ctypes.data_as(_abi.FP),
+                       flags.ctypes.data_as(_abi.U8P)), "esdf")
+        return dist, flags
+
     def extract_triangle_mesh(self, fill_holes=True, min_weight=0.0, table="generated",
                               halo=None):
         """VDBVolume.extract_triangle_mesh: (vertices (3T, 3) float32, triangles (T, 3) int64) —
@@ -692,6 +736,21 @@ class HipTSDFVolume(TSDFVolume):
                        C.c_void_p(int(d_depth_ptr or 0)), C.c_void_p(int(d_normal_ptr or 0)),
                        C.c_void_p(int(d_hit_ptr or 0))), "raycast_device")
         del keep
+
+    def esdf_device(self, lo, hi, max_dist, site_band=None, min_weight=0.0, flags=True):
+        """`esdf` into device tensors on the volume's GPU: (dist [z, y, x] float32, flags [z, y, x]
+        uint8, or None with flags=False), complete when the call returns."""
+        import torch
+        lo, hi, radius, band = self._esdf_args(lo, hi, max_dist, site_band)
+        fn = self._esdf_fn("tsdf_esdf_dense_device")
+        shape = tuple(int(d) for d in (hi - lo)[::-1])
+        dist = torch.empty(shape, dtype=torch.float32, device=self.tensor_device)
+        fl = torch.empty(shape, dtype=torch.uint8, device=self.tensor_device) if flags else None
+        torch.cuda.synchronize(dist.device)
+        self._check(fn(self._ctx, lo.ctypes.data_as(_abi.L3), hi.ctypes.data_as(_abi.L3), radius,
+                       band, float(min_weight), C.c_void_p(dist.data_ptr()),
+                       C.c_void_p(fl.data_ptr() if flags else 0)), "esdf_device")
+        return dist, fl
 
     def align_terms(self, points, pose, min_weight=0.0, n=None):
         """Gauss-Newton terms of the point-to-TSDF error of a cloud under `pose` (3x4 or 4x4, world
