@@ -8,6 +8,8 @@
 //                which the integrate's range filter drops), then the scan pose (fp32, 3x4).
 // One lane per pixel of one packet column: the column's header is read once per lane (broadcast
 // in L1), the pixel fields are byte-gathered (layouts are byte-packed, not aligned).
+// Two different valid columns with the same measurement_id in one frame are written by separate
+// workgroups, so which of them the image keeps is not defined (identical repeats are harmless).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 

@@ -296,3 +296,163 @@ def test_refine_pose(maps, scan0):
     assert np.sqrt(e / nv) < steps[0]["rms"]
     with pytest.raises(align.AlignError):
         align.refine_pose(m.vol, pts[:4] + 1000.0, np.eye(4))
+
+
+# ---- the align sums and k_sample at the counts that break reductions ------------------------------
+
+ALIGN_CAP = 1024 * 256        # ALIGN_MAX_WG workgroups of 256 lanes: one pass of k_align
+N_LONG = ALIGN_CAP + 321      # ... and 321 points of a second pass
+N_PAST_GRID = 8192 * 256 + 77  # past k_sample's grid cap
+COUNTS = [1, 2, 63, 64, 65, 255, 256, 257, 1000]
+
+
+def words(H, b, e, nv):
+    """The 44 output words: H row-major, b, e, n_valid."""
+    return np.concatenate([np.asarray(H, np.float64).reshape(36), b, [e, nv]])
+
+
+def check_align(m, pts, pose, mw=0.0, got=None):
+    """n_valid exactly; each of the 43 sums within n_valid 2^-52 sum|term| of the reference's
+    double sum, the bound of any summation order of the same double terms (the kernel forms each
+    term in double from the same fp32 values); with at most one term there is nothing to reorder,
+    and the sums must be equal.  Returns (the 44 words, n_valid)."""
+    H, b, e, nv, ab = sr.align_terms(m.field, pts, pose, mw)
+    if got is None:
+        got = m.vol.align_terms(pts, pose, mw)
+    g, ref = words(*got), words(H, b, e, nv)
+    assert got[3] == nv
+    err = np.abs(g[:43] - ref[:43])
+    if nv <= 1:
+        assert np.array_equal(g, ref)
+    else:
+        tol = nv * 2.0 ** -52 * ab[:43]
+        assert np.all(err <= tol), (err / tol).max()
+    assert np.array_equal(got[0], got[0].T)
+    return g, nv
+
+
+def slice_with(valid, n):
+    """The start of the first run of n consecutive queries that has a valid one (n = 1), exactly
+    one valid and one invalid (n = 2), or at least one of each."""
+    c = np.concatenate([[0], np.cumsum(valid.astype(np.int64))])
+    k = c[n:] - c[:-n]  # valid ones in [i, i + n)
+    ok = (k == 1) if n <= 2 else (k >= 1) & (k < n)
+    return int(np.argmax(ok)) if ok.any() else None
+
+
+def far(pts):
+    """The same points 1000 m away: no map there, every sample invalid."""
+    return np.ascontiguousarray(np.asarray(pts, F) + F(1000.0))
+
+
+@pytest.fixture(scope="module")
+def long_cloud(sim, scan0):
+    """N_LONG points: scans 0, 1 and 2 concatenated and cut (two scans hold 262 144 points at the
+    most, one short of a second pass)."""
+    p = np.concatenate([scan0[0], sim.scan(1)[0], sim.scan(2)[0]])
+    assert p.shape[0] >= N_LONG
+    return np.ascontiguousarray(p[:N_LONG])
+
+
+@pytest.mark.parametrize("n", COUNTS)
+def test_align_counts(maps, queries, n):
+    """A lane alone, partial waves, a partial workgroup, whole ones and one lane more."""
+    m = maps["vdbfusion_f64"]
+    pose = sr.start_pose()
+    valid = sr.sample(m.field, sr.transform(pose, queries), sr.TRILINEAR)[3].astype(bool)
+    k0 = slice_with(valid, n)
+    assert k0 is not None
+    pts = np.ascontiguousarray(queries[k0:k0 + n])
+    g, nv = check_align(m, pts, pose)
+    assert (nv == 1) if n <= 2 else (1 <= nv < n)
+    print("n %d at %d: n_valid %d" % (n, k0, nv))
+    if n == 257:  # the same bits on every call
+        assert np.array_equal(words(*m.vol.align_terms(pts, pose)).view(np.uint64),
+                              g.view(np.uint64))
+
+
+def test_align_no_valid_point(maps, queries):
+    m = maps["vdbfusion_f64"]
+    for n in (1, 300, 5000):
+        g, nv = check_align(m, far(queries[:n]), sr.start_pose())
+        assert nv == 0 and not g.view(np.uint64).any()  # all 44 words exactly +0
+
+
+def test_align_only_the_last_of_300_is_valid(maps, queries):
+    """One workgroup and a wave of the next without a valid point, then a lone valid lane."""
+    m = maps["vdbfusion_f64"]
+    pose = np.eye(4)[:3]
+    valid = m.reference(queries, "trilinear", 0.0)[3].astype(bool)
+    pts = far(queries[:300])
+    pts[299] = queries[np.argmax(valid)]
+    g, nv = check_align(m, pts, pose)
+    assert nv == 1 and g[42] > 0
+
+
+def test_align_second_pass(maps, long_cloud):
+    """More points than ALIGN_MAX_WG x 256: 321 lanes accumulate over two passes.  Then the same
+    cloud with every point of the first pass made invalid, so that only second-pass lanes hold
+    anything; and the same bits on every call."""
+    m = maps["vdbfusion_f64"]
+    pose = sr.start_pose()
+    g, nv = check_align(m, long_cloud, pose)
+    tail = check_align(m, long_cloud[ALIGN_CAP:], pose)[1]
+    print("long cloud: n_valid %d, %d of them in the second pass" % (nv, tail))
+    assert nv >= 1000 and tail >= 10
+    assert np.array_equal(words(*m.vol.align_terms(long_cloud, pose)).view(np.uint64),
+                          g.view(np.uint64))
+    only = long_cloud.copy()
+    only[:ALIGN_CAP] = far(only[:ALIGN_CAP])
+    g2, nv2 = check_align(m, only, pose)
+    assert nv2 == tail and g2[42] > 0
+
+
+def test_align_on_the_voxblox_map(maps, scan0):
+    """Background 0 instead of tau."""
+    m = maps["voxblox"]
+    pts = np.ascontiguousarray(scan0[0][::8])
+    g, nv = check_align(m, pts, sr.start_pose())
+    print("voxblox: n_valid %d" % nv)
+    assert nv >= 1000
+
+
+def test_align_device_pointer_unaligned(maps, scan0):
+    """The device-pointer form on points 12 bytes into an allocation (not 16-byte aligned)."""
+    import torch
+    m = maps["vdbfusion_f64"]
+    pts = np.ascontiguousarray(scan0[0][::8][:4099])
+    pose = sr.start_pose()
+    g, nv = check_align(m, pts, pose)
+    assert nv >= 100
+    d = torch.full((pts.shape[0] + 2, 3), 1000.0, dtype=torch.float32, device=m.vol.tensor_device)
+    d[1:-1] = torch.from_numpy(pts).to(d.device)
+    torch.cuda.synchronize(d.device)
+    ptr = d.data_ptr() + 12
+    assert d.data_ptr() % 16 == 0 and ptr % 16 != 0
+    got = m.vol.align_terms(ptr, pose, n=pts.shape[0])
+    assert np.array_equal(words(*got).view(np.uint64), g.view(np.uint64))
+
+
+def tiled_queries(points, origin, n):
+    """n queries: the scan's query points (every 8th with range > 0.5 m) tiled, each tile with a
+    fresh seeded +-5 cm jitter."""
+    q = np.asarray(points, F)[::8]
+    rng_m = np.linalg.norm(q.astype(np.float64) - np.asarray(origin, np.float64), axis=1)
+    q = q[rng_m > 0.5]
+    tiles = []
+    for t in range(-(-n // q.shape[0])):
+        jit = np.random.default_rng(1000 + t).uniform(-0.05, 0.05, q.shape)
+        tiles.append((q + jit).astype(F))
+    return np.ascontiguousarray(np.concatenate(tiles)[:n])
+
+
+def test_sample_device_past_the_grid_cap(maps, scan0):
+    """More queries than 8192 x 256: 77 lanes of k_sample run the loop body twice."""
+    m = maps["vdbfusion_f64"]
+    q = tiled_queries(*scan0, N_PAST_GRID)
+    assert q.shape[0] == N_PAST_GRID
+    ref = sr.sample(m.field, q, sr.TRILINEAR)
+    share = ref[3].mean()
+    print("past the grid cap: %.1f %% valid, %d of the last 77" % (100 * share, ref[3][-77:].sum()))
+    assert 0.30 <= share <= 0.60 and 0 < ref[3][-77:].sum() < 77
+    assert_same(sample_device(m.vol, q, "trilinear"), ref)
