@@ -29,6 +29,7 @@
 
 #include "../../include/tsdf_hip.h"
 #include "../../include/tsdf_hip_esdf.h"
+#include "../../include/tsdf_hip_merge.h"
 #include "../../include/tsdf_hip_prune.h"
 #include "../../include/tsdf_hip_raycast.h"
 #include "../../include/tsdf_hip_sample.h"
@@ -37,6 +38,7 @@
 #include "ctx_plan.h"
 #include "esdf_plan.h"
 #include "host_pack.h"
+#include "merge_plan.h"
 #include "pack_pool.h"
 #include "prune_plan.h"
 #include "tsdf_device.h"
@@ -2545,6 +2547,125 @@ int tsdf_import_bricks(tsdf_ctx* c, const int32_t* coords, const float* sdf, con
     HIPCHK(c, launch_import(c->T, c->Pl, dc, (uint32_t)n, ds, dw, dt, c->G, merge_cap(c), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return tsdf_sync(c);
+}
+
+}  // extern "C"
+
+// ---- merging a map into another under a rigid transform (include/tsdf_hip_merge.h; kernels in
+// tsdf_merge.hip; the pose, the candidate search and the scratch sizes: merge_plan.h)
+
+// One context's part of the entry rules: the state rules of the read-side calls
+static int merge_ctx_state(tsdf_ctx* d, tsdf_ctx* c, const char* which) {
+    if (c->p.n_sectors > 1)
+        return fail(d, TSDF_EINVAL, "merge: the %s context holds one sector shard of the map "
+                                    "(n_sectors > 1); merging a sharded field is not supported", which);
+    if (c->brd_open)
+        return fail(d, TSDF_EINVAL, "merge: a border reduce is open on the %s context: commit or "
+                                    "abort it first (tsdf_border_commit_device)", which);
+    return TSDF_OK;
+}
+
+static int merge_impl(tsdf_ctx* d, tsdf_ctx* s, const double* pose, int32_t mode, float min_weight,
+                      tsdf_merge_stats* out, bool apply) {
+    if (!d) return TSDF_EINVAL;
+    if (!s) return fail(d, TSDF_EINVAL, "merge: the source context is NULL");
+    if (s == d) return fail(d, TSDF_EINVAL, "merge: source and destination are the same context");
+    if (!apply && !out) return fail(d, TSDF_EINVAL, "merge: null argument");
+    MergeXform X;
+    int rule = merge_xform(pose, mode, min_weight, (double)d->R.vs, &X);
+    if (rule) return fail(d, TSDF_EINVAL, "merge: %s", merge_arg_text(rule));
+    if (s->device != d->device)
+        return fail(d, TSDF_EINVAL, "merge: the contexts are on different devices (%d and %d)",
+                    d->device, s->device);
+    rule = merge_compat(d->p.voxel_size, s->p.voxel_size, d->p.sdf_trunc, s->p.sdf_trunc,
+                        d->p.semantics, s->p.semantics);
+    if (rule) return fail(d, TSDF_EINVAL, "merge: %s", merge_compat_text(rule));
+    int rc = merge_ctx_state(d, d, "destination");
+    if (!rc) rc = merge_ctx_state(d, s, "source");
+    if (rc) return rc;
+    HIPCHK(d, hipSetDevice(d->device));  // (both contexts': the scratch and every launch below)
+    uint64_t n_src = 0, n_dst = 0;
+    rc = pool_bricks(s, &n_src);
+    if (rc) return fail(d, rc, "merge: the source context failed: %s", s->err.c_str());
+    rc = pool_bricks(d, &n_dst);
+    if (rc) return rc;
+    tsdf_merge_stats st{};
+    st.src_bricks = n_src;
+    if (out) *out = st;
+    if (!n_src) return TSDF_OK;
+
+    Scratch tmp;
+    unsigned long long* ctr = nullptr;
+    std::vector<unsigned long long> hc(MERGE_CTR_WORDS, 0);
+    unsigned long long h[6] = {0, 0, 0, 0, 0, 0};
+    HIPCHK(d, tmp.get(d, &ctr, MERGE_CTR_WORDS));
+    HIPCHK(d, hipMemsetAsync(ctr, 0, MERGE_CTR_WORDS * 8, d->stream));
+    HIPCHK(d, launch_merge_pairs(s->T.brick_keys, (uint32_t)n_src, X, mode, ctr, d->stream));
+    HIPCHK(d, hipMemcpyAsync(h, ctr, 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
+    const uint64_t pairs = h[0];
+    if (!pairs) return TSDF_OK;  // the image lies outside the index domain
+    if (pairs >= MERGE_MAX_PAIRS)
+        return fail(d, TSDF_ENOMEM, "merge: %llu candidate bricks", (unsigned long long)pairs);
+    const uint64_t slots = merge_set_slots(pairs);
+    uint64_t *set = nullptr, *list = nullptr;
+    uint32_t *flag = nullptr, *tslot = nullptr;
+    if (tmp.get(d, &set, slots) != hipSuccess || tmp.get(d, &list, pairs) != hipSuccess ||
+        tmp.get(d, &flag, pairs) != hipSuccess || tmp.get(d, &tslot, pairs) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(d, TSDF_ENOMEM, "merge: no device memory for %llu bytes of scratch",
+                    (unsigned long long)merge_scratch_bytes(pairs));
+    }
+    HIPCHK(d, launch_fill_u64(set, EMPTY_KEY, slots, d->stream));
+    HIPCHK(d, launch_merge_candidates(s->T.brick_keys, (uint32_t)n_src, X, mode, set, slots, list,
+                                      pairs, ctr, d->stream));
+    HIPCHK(d, launch_merge_flag(d->T, d->Pl, s->T, s->Pl, s->R, X, mode, min_weight, list, pairs,
+                                ctr, flag, d->stream));
+    HIPCHK(d, hipMemcpyAsync(hc.data(), ctr, MERGE_CTR_WORDS * 8, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
+    h[1] = hc[1];
+    for (uint32_t q = 0; q < MERGE_SHARDS; q++)  // the flag kernel's counter shards
+        for (int k = 0; k < 4; k++) h[2 + k] += hc[MERGE_CTR_HEAD + q * MERGE_SHARD_WORDS + k];
+    const uint64_t n_cand = h[1];
+    if (n_cand > pairs || h[3] > h[2] || h[2] > n_cand || h[5] > h[4])
+        return fail(d, TSDF_EHIP, "merge: inconsistent counts (%llu candidates of %llu pairs)",
+                    (unsigned long long)n_cand, (unsigned long long)pairs);
+    st.candidate_bricks = n_cand;
+    st.touched_bricks = h[2];
+    st.new_bricks = h[3];
+    st.merged_voxels = h[4];
+    st.overlap_voxels = h[5];
+    if (out) *out = st;
+    if (!apply || !st.touched_bricks) return TSDF_OK;
+
+    // room for the new bricks before anything is written (a merge is not a replayable batch)
+    const uint64_t need = n_dst + st.new_bricks;
+    if (need > d->T.max_bricks) {
+        if (!d->can_grow || (d->p.max_bricks_hard && need > d->p.max_bricks_hard) ||
+            need > 0xFFFFFFEFull)
+            return fail(d, TSDF_ENOMEM, "merge: %llu new bricks do not fit the pool (%llu of %llu "
+                                        "bricks in use) and it cannot grow",
+                        (unsigned long long)st.new_bricks, (unsigned long long)n_dst,
+                        (unsigned long long)d->T.max_bricks);
+        rc = grow_capacity(d, need);
+        if (rc) return rc;
+    }
+    HIPCHK(d, launch_merge_apply(d->T, d->Pl, s->T, s->Pl, s->R, X, mode, min_weight, merge_cap(d),
+                                 list, n_cand, flag, tslot, d->G, d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
+    return tsdf_sync(d);
+}
+
+extern "C" {
+
+int tsdf_merge_count(tsdf_ctx* dst, tsdf_ctx* src, const double pose[12], int32_t mode,
+                     float min_weight, tsdf_merge_stats* out) {
+    return merge_impl(dst, src, pose, mode, min_weight, out, false);
+}
+
+int tsdf_merge_transformed(tsdf_ctx* dst, tsdf_ctx* src, const double pose[12], int32_t mode,
+                           float min_weight, tsdf_merge_stats* out) {
+    return merge_impl(dst, src, pose, mode, min_weight, out, true);
 }
 
 }  // extern "C"

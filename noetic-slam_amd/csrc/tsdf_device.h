@@ -514,5 +514,31 @@ hipError_t launch_rm_gather(const Pool& Pl, const uint32_t* d_slots, uint32_t m,
 // brick d_mover[i] -> slot d_hole[i] (voxels and the slot's key), i < n_moves
 hipError_t launch_rm_move(const Table& T, const Pool& Pl, const uint32_t* d_hole,
                           const uint32_t* d_mover, uint32_t n_moves, hipStream_t st);
+// merging a map into another under a rigid transform (tsdf_merge.hip; include/tsdf_hip_merge.h;
+// the pose and the candidate search: merge_plan.h).  d_ctr: MERGE_CTR_WORDS u64, zeroed by the
+// caller -- [0] candidate pairs, [1] distinct candidates (the list's entries), then from
+// MERGE_CTR_HEAD on MERGE_SHARDS shards of MERGE_SHARD_WORDS words, of which the first four are
+// touched bricks, new bricks, merged voxels, overlap voxels (the caller adds the shards).
+// Td / Pd: the destination, Ts / Ps: the source.
+struct MergeXform;
+constexpr uint32_t MERGE_SHARDS = 64, MERGE_SHARD_WORDS = 16, MERGE_CTR_HEAD = 16;
+constexpr uint32_t MERGE_CTR_WORDS = MERGE_CTR_HEAD + MERGE_SHARDS * MERGE_SHARD_WORDS;
+hipError_t launch_merge_pairs(const uint64_t* d_src_keys, uint32_t n_src, const MergeXform& X,
+                              int mode, unsigned long long* d_ctr, hipStream_t st);
+// d_set: set_slots (a power of two, >= 2 * pairs) keys, EMPTY_KEY; d_list: list_cap >= pairs keys
+hipError_t launch_merge_candidates(const uint64_t* d_src_keys, uint32_t n_src, const MergeXform& X,
+                                   int mode, uint64_t* d_set, uint64_t set_slots, uint64_t* d_list,
+                                   uint64_t list_cap, unsigned long long* d_ctr, hipStream_t st);
+// d_flag[b] per candidate: 0 no valid sample, 1 valid and held by dst, 3 valid and new
+hipError_t launch_merge_flag(const Table& Td, const Pool& Pd, const Table& Ts, const Pool& Ps,
+                             const RayConst& R, const MergeXform& X, int mode, float min_w,
+                             const uint64_t* d_list, uint64_t list_cap, unsigned long long* d_ctr,
+                             uint32_t* d_flag, hipStream_t st);
+// the flagged candidates of d_list[0, n) inserted into dst (d_tslot: their pool slots) and fused
+hipError_t launch_merge_apply(const Table& Td, const Pool& Pd, const Table& Ts, const Pool& Ps,
+                              const RayConst& R, const MergeXform& X, int mode, float min_w,
+                              float max_w, const uint64_t* d_list, uint64_t n,
+                              const uint32_t* d_flag, uint32_t* d_tslot, Globals* G,
+                              hipStream_t st);
 
 }  // namespace tsdf

@@ -159,18 +159,23 @@ __device__ __forceinline__ uint32_t straddle_mask(const Base& b) {
     return ((b.x & 7) == 7 ? 1u : 0u) | ((b.y & 7) == 7 ? 2u : 0u) | ((b.z & 7) == 7 ? 4u : 0u);
 }
 
+// VALUES = false (the map merge's validity pass, tsdf_merge.hip): the sample's weight and validity
+// alone, decided exactly as below; no distance is read and s, gx, gy, gz are not meaningful.
+
 // the nearest sample of base voxel b in the brick at pool slot `slot`
+template <bool VALUES = true>
 __device__ __forceinline__ Sample eval_nearest(const Pool& Pl, float bg, float min_w, const Base& b,
                                                uint32_t slot) {
     Sample r{bg, 0.0f, 0.0f, 0.0f, 0.0f, false};
     const size_t i = (size_t)slot * BRICK_VOX + (((b.z & 7) << 6) | ((b.y & 7) << 3) | (b.x & 7));
-    r.s = Pl.sdf[i];
+    if constexpr (VALUES) r.s = Pl.sdf[i];
     r.w = Pl.weight[i];
     r.valid = r.w > 0.0f && r.w >= min_w;
     return r;
 }
 
 // the trilinear sample of the cube at base voxel b, its corners' bricks at pool slots cslot
+template <bool VALUES = true>
 __device__ __forceinline__ Sample eval_trilinear(const Pool& Pl, float inv, float bg, float min_w,
                                                  const Base& b, const uint32_t (&cslot)[8]) {
     const int lx = b.x & 7, ly = b.y & 7, lz = b.z & 7;
@@ -191,6 +196,13 @@ __device__ __forceinline__ Sample eval_trilinear(const Pool& Pl, float inv, floa
     for (int c = 0; c < 8; c++) {
         all = all && w[c] > 0.0f && w[c] >= min_w;
         wmin = fminf(wmin, w[c]);
+    }
+    if constexpr (!VALUES) {
+        if (all) {
+            r.w = wmin;
+            r.valid = true;
+        }
+        return r;
     }
     if (all) {
         float s[8];
@@ -215,24 +227,26 @@ __device__ __forceinline__ Sample eval_trilinear(const Pool& Pl, float inv, floa
 }
 
 // The voxel floorf(p * inv): its (S, W), (bg, 0) where unallocated or outside |i| < 2^23.
+template <bool VALUES = true>
 __device__ __forceinline__ Sample sample_nearest(const Table& T, const Pool& Pl, float inv, float bg,
                                                  float min_w, bool live, float px, float py,
                                                  float pz) {
     const Base b = base_nearest(inv, live, px, py, pz);
     uint32_t cslot[1];
     const bool ok = resolve<1>(T, b.inside, b.x >> 3, b.y >> 3, b.z >> 3, 0u, cslot);
-    if (ok) return eval_nearest(Pl, bg, min_w, b, cslot[0]);
+    if (ok) return eval_nearest<VALUES>(Pl, bg, min_w, b, cslot[0]);
     return Sample{bg, 0.0f, 0.0f, 0.0f, 0.0f, false};
 }
 
 // The trilinear interpolant of the 8 voxel centres around p and its gradient (tsdf_hip_sample.h).
+template <bool VALUES = true>
 __device__ __forceinline__ Sample sample_trilinear(const Table& T, const Pool& Pl, float inv,
                                                    float bg, float min_w, bool live, float px,
                                                    float py, float pz) {
     const Base b = base_trilinear(inv, live, px, py, pz);
     uint32_t cslot[8];
     const bool ok = resolve<8>(T, b.inside, b.x >> 3, b.y >> 3, b.z >> 3, straddle_mask(b), cslot);
-    if (ok) return eval_trilinear(Pl, inv, bg, min_w, b, cslot);
+    if (ok) return eval_trilinear<VALUES>(Pl, inv, bg, min_w, b, cslot);
     return Sample{bg, 0.0f, 0.0f, 0.0f, 0.0f, false};
 }
 

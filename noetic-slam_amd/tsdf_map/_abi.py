@@ -216,6 +216,24 @@ ESDF_SIGNATURES = {
     "tsdf_esdf_dense_device": (C.c_int, [P, L3, L3, C.c_uint32, C.c_float, C.c_float, P, P]),
 }
 
+# include/tsdf_hip_merge.h (TSDF_MERGE_API): one map merged into another under a rigid transform,
+# likewise a feature of libtsdf_hip.so outside the contract, declared on the HIP library only.
+# Modes: SAMPLE_MODES.
+class MergeStats(C.Structure):
+    """tsdf_merge_stats (include/tsdf_hip_merge.h)."""
+    _fields_ = [("src_bricks", C.c_uint64), ("candidate_bricks", C.c_uint64),
+                ("touched_bricks", C.c_uint64), ("new_bricks", C.c_uint64),
+                ("merged_voxels", C.c_uint64), ("overlap_voxels", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+MERGE_SIGNATURES = {
+    "tsdf_merge_count": (C.c_int, [P, P, D3, C.c_int32, C.c_float, C.POINTER(MergeStats)]),
+    "tsdf_merge_transformed": (C.c_int, [P, P, D3, C.c_int32, C.c_float, C.POINTER(MergeStats)]),
+}
+
 
 def declare(lib, names=None, optional=(), table=None):
     """Attach restype/argtypes for the ABI symbols present in `lib`; raise if a required one is

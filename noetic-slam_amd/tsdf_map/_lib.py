@@ -40,6 +40,8 @@ def load_hip_library(path=None):
     _abi.declare(lib, table=_abi.PRUNE_SIGNATURES)
     # ... and the distance field of a box (include/tsdf_hip_esdf.h)
     _abi.declare(lib, table=_abi.ESDF_SIGNATURES)
+    # ... and merging a map into another under a rigid transform (include/tsdf_hip_merge.h)
+    _abi.declare(lib, table=_abi.MERGE_SIGNATURES)
     if lib.tsdf_abi_version() != ABI_VERSION:
         raise RuntimeError("libtsdf_hip.so ABI version mismatch")
     if path is None:

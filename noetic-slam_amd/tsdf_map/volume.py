@@ -508,6 +508,46 @@ class TSDFVolume:
             return coords[:k], s[:k], w[:k]
         raise TsdfError(_abi.TSDF_EOVERFLOW, "evict_outside: brick count kept changing")
 
+    # -- merging another map into this one (include/tsdf_hip_merge.h) ----------------------------
+    def _merge_fn(self, name):
+        """An entry point of include/tsdf_hip_merge.h, detected by the symbol like `_sample_fn`."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (merging maps under a transform is "
+                                      "part of libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    def merge_from(self, src, pose, mode="trilinear", min_weight=0.0, dry_run=False):
+        """Merge the map of `src` into this one at `pose` = T_dst_src ((3, 4) or (4, 4),
+        x_dst = R x_src + t): `src` is resampled at this volume's voxel centres (mode "nearest" or
+        "trilinear", valid where `sample` is) and fused by weight, on the GPU.  Resampling is not
+        copying: the trilinear mode keeps only fully observed cubes.  dry_run: change nothing.
+        Returns the counts of tsdf_merge_stats as a dict; on TsdfError (TSDF_ENOMEM: the new
+        bricks do not fit and the pool cannot grow) both maps are as they were and the error's
+        `stats` holds the counts.  include/tsdf_hip_merge.h states the rules."""
+        if mode not in _abi.SAMPLE_MODES:
+            raise ValueError("mode must be one of %s" % sorted(_abi.SAMPLE_MODES))
+        fn = self._merge_fn("tsdf_merge_count" if dry_run else "tsdf_merge_transformed")
+        if not isinstance(src, TSDFVolume):
+            raise TypeError("src must be a TSDFVolume")
+        if src._lib is not self._lib:
+            raise ValueError("src belongs to another library")
+        T = np.asarray(pose, np.float64)
+        if T.shape == (4, 4):
+            T = T[:3]
+        if T.shape != (3, 4):
+            raise ValueError("pose must be a (3, 4) or (4, 4) matrix")
+        T = np.ascontiguousarray(T)
+        st = _abi.MergeStats()
+        rc = fn(self._ctx, src._ctx, _d3(T), _abi.SAMPLE_MODES[mode], float(min_weight),
+                C.byref(st))
+        try:
+            self._check(rc, "merge_from")
+        except TsdfError as e:
+            e.stats = st.as_dict()
+            raise
+        return st.as_dict()
+
     def save(self, path):
         """Checkpoint: the brick map as .npz (keys, sdf, weight, parameters)."""
         c, s, w = self.export_bricks()
@@ -691,6 +731,32 @@ class HipTSDFVolume(TSDFVolume):
             v.tensor_device = "cuda:%d" % q.device_id
             vols.append(v)
         return vols
+
+    def empty_like(self):
+        """A new, empty volume with this one's parameters (on the same device)."""
+        out = type(self).__new__(type(self))
+        out._lib = self._lib
+        out._ctx = C.c_void_p()
+        p = _abi.TsdfParams.from_buffer_copy(self.params)
+        rc = self._lib.tsdf_create(C.byref(p), C.byref(out._ctx))
+        if rc != _abi.TSDF_OK:
+            out._ctx = C.c_void_p()
+            raise TsdfError(rc, "tsdf_create failed (empty_like)")
+        out._adopt(p)
+        out.tensor_device = self.tensor_device
+        return out
+
+    def transformed(self, pose, **kw):
+        """A new volume with this one's parameters, holding this map moved by `pose` (T_new_this):
+        `merge_from(self, pose, **kw)` into an empty volume.  This volume is not changed."""
+        self._merge_fn("tsdf_merge_transformed")
+        out = self.empty_like()
+        try:
+            out.merge_from(self, pose, **kw)
+        except Exception:
+            out.close()
+            raise
+        return out
 
     def integrate_device(self, d_xyz_ptr, n, extrinsic):
         o = _origin_of(extrinsic)
