@@ -30,6 +30,7 @@
 #include "../../include/tsdf_hip.h"
 #include "../../include/tsdf_hip_esdf.h"
 #include "../../include/tsdf_hip_merge.h"
+#include "../../include/tsdf_hip_mesh.h"
 #include "../../include/tsdf_hip_prune.h"
 #include "../../include/tsdf_hip_raycast.h"
 #include "../../include/tsdf_hip_sample.h"
@@ -39,6 +40,7 @@
 #include "esdf_plan.h"
 #include "host_pack.h"
 #include "merge_plan.h"
+#include "mesh_plan.h"
 #include "pack_pool.h"
 #include "prune_plan.h"
 #include "tsdf_device.h"
@@ -2481,7 +2483,120 @@ static int mesh_impl(tsdf_ctx* c, float min_weight, int32_t table, const uint32_
     return TSDF_OK;
 }
 
+// ---- indexed mesh (include/tsdf_hip_mesh.h) ------------------------------------------------------
+
+// What a call of the indexed mesh wants: counts only, host outputs or device outputs.
+enum MeshOut { MESH_COUNT, MESH_HOST, MESH_DEVICE };
+
+static int mesh_indexed_impl(tsdf_ctx* c, float min_weight, int32_t table, const int64_t* lo,
+                             const int64_t* hi, float* vertices, float* normals,
+                             uint32_t* triangles, uint64_t cap_v, uint64_t cap_t,
+                             tsdf_mesh_counts* out, MeshOut mode) {
+    if (!c) return TSDF_EINVAL;
+    if (!out) return fail(c, TSDF_EINVAL, "mesh: null counts");
+    if (table < 0 || table >= TSDF_MC_TABLES)
+        return fail(c, TSDF_EINVAL, "mesh: unknown marching-cubes table %d", table);
+    MeshBox B;
+    bool empty = false;
+    const int a = mesh_box_check(lo, hi, &B, &empty);
+    int rc = map_query_args(c, "mesh", "an indexed mesh of", TSDF_SAMPLE_NEAREST, min_weight,
+                            a == MESH_ARG_OK ? nullptr : mesh_arg_text(a));
+    if (rc) return rc;
+    uint64_t n_pool = 0;
+    rc = pool_bricks(c, &n_pool);  // flushes and drains
+    if (rc) return rc;
+    *out = tsdf_mesh_counts{0, 0, 0};
+    if (!n_pool || empty) return TSDF_OK;
+    if (n_pool >= 0xFFFFFFFFull) return fail(c, TSDF_EINVAL, "mesh: too many bricks");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the map's bricks in (z, y, x) order (the soup's order), then those the box lists
+    std::vector<uint64_t> all(n_pool), keys;
+    HIPCHK(c, hipMemcpy(all.data(), c->T.brick_keys, n_pool * 8, hipMemcpyDeviceToHost));
+    std::sort(all.begin(), all.end(), brick_key_less_zyx);
+    out->n_bricks = mesh_list_bricks(all, B, &keys);
+    const uint64_t nb = keys.size();
+    if (!out->n_bricks) return TSDF_OK;
+    Scratch tmp;
+    uint64_t *dk = nullptr, *dtoff = nullptr;
+    uint32_t *dmask = nullptr, *dcnt = nullptr, *dvbase = nullptr, *dsi = nullptr;
+    hipError_t e = tmp.get(c, &dk, nb);
+    if (e == hipSuccess) e = tmp.get(c, &dsi, n_pool);  // pool slot -> position in the list
+    if (e == hipSuccess) e = tmp.get(c, &dmask, nb * MESH_VMASK_WORDS);
+    if (e == hipSuccess) e = tmp.get(c, &dcnt, 2 * nb);  // triangles, then vertices
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, TSDF_ENOMEM, "mesh: scratch allocation for %llu bricks failed",
+                    (unsigned long long)nb);
+    }
+    std::vector<uint32_t> cnt(2 * nb), vbase(nb);
+    std::vector<uint64_t> toff(nb);
+    HIPCHK(c, hipMemcpyAsync(dk, keys.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_mesh_mark(c->T, c->Pl, dk, (uint32_t)nb, min_weight, table, B,
+                               (uint32_t)n_pool, dsi, dmask, dcnt, dcnt + nb, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), dcnt, 2 * nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    uint64_t n_tri = 0, n_vert = 0;
+    mesh_prefix(cnt.data(), cnt.data() + nb, nb, toff.data(), vbase.data(), &n_tri, &n_vert);
+    if (n_vert >= (1ull << 32))
+        return fail(c, TSDF_EINVAL, "mesh: %llu vertices do not fit 32-bit indices; mesh it in "
+                                    "boxes", (unsigned long long)n_vert);
+    out->n_vertices = n_vert;
+    out->n_triangles = n_tri;
+    if (mode == MESH_COUNT || !n_tri) return TSDF_OK;
+    if (n_vert > cap_v || n_tri > cap_t)
+        return fail(c, TSDF_EOVERFLOW, "mesh has %llu vertices and %llu triangles",
+                    (unsigned long long)n_vert, (unsigned long long)n_tri);
+    if (!vertices || !triangles) return fail(c, TSDF_EINVAL, "mesh: null buffer");
+    float *dv = vertices, *dn = normals;
+    uint32_t* dt = triangles;
+    e = tmp.get(c, &dtoff, nb);
+    if (e == hipSuccess) e = tmp.get(c, &dvbase, nb);
+    if (mode == MESH_HOST) {  // staged on the device
+        if (e == hipSuccess) e = tmp.get(c, &dv, 3 * n_vert);
+        if (e == hipSuccess && normals) e = tmp.get(c, &dn, 3 * n_vert);
+        if (e == hipSuccess) e = tmp.get(c, &dt, 3 * n_tri);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, TSDF_ENOMEM, "mesh: output allocation for %llu vertices and %llu triangles "
+                                    "failed", (unsigned long long)n_vert, (unsigned long long)n_tri);
+    }
+    HIPCHK(c, hipMemcpyAsync(dtoff, toff.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dvbase, vbase.data(), nb * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_mesh_fill(c->T, c->Pl, dk, (uint32_t)nb, min_weight, table, B, c->R.vs,
+                               c->R.inv_vs, (uint32_t)n_pool, dsi, dmask, dcnt, dcnt + nb, dtoff,
+                               dvbase, dv, dn, dt, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (mode == MESH_HOST) {
+        HIPCHK(c, hipMemcpy(vertices, dv, n_vert * 12, hipMemcpyDeviceToHost));
+        if (normals) HIPCHK(c, hipMemcpy(normals, dn, n_vert * 12, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(triangles, dt, n_tri * 12, hipMemcpyDeviceToHost));
+    }
+    return TSDF_OK;
+}
+
 extern "C" {
+
+int tsdf_mesh_indexed_count(tsdf_ctx* c, float min_weight, int32_t table, const int64_t lo[3],
+                            const int64_t hi[3], tsdf_mesh_counts* out) {
+    return mesh_indexed_impl(c, min_weight, table, lo, hi, nullptr, nullptr, nullptr, 0, 0, out,
+                             MESH_COUNT);
+}
+
+int tsdf_mesh_indexed(tsdf_ctx* c, float min_weight, int32_t table, const int64_t lo[3],
+                      const int64_t hi[3], float* vertices, float* normals, uint32_t* triangles,
+                      uint64_t cap_vertices, uint64_t cap_triangles, tsdf_mesh_counts* out) {
+    return mesh_indexed_impl(c, min_weight, table, lo, hi, vertices, normals, triangles,
+                             cap_vertices, cap_triangles, out, MESH_HOST);
+}
+
+int tsdf_mesh_indexed_device(tsdf_ctx* c, float min_weight, int32_t table, const int64_t lo[3],
+                             const int64_t hi[3], float* vertices, float* normals,
+                             uint32_t* triangles, uint64_t cap_vertices, uint64_t cap_triangles,
+                             tsdf_mesh_counts* out) {
+    return mesh_indexed_impl(c, min_weight, table, lo, hi, vertices, normals, triangles,
+                             cap_vertices, cap_triangles, out, MESH_DEVICE);
+}
 
 int tsdf_mc_table(uint8_t* out) {
     if (!out) return TSDF_EINVAL;

@@ -464,6 +464,25 @@ hipError_t launch_mesh_count(const Table& T, const Pool& Pl, const Table& H, con
 hipError_t launch_mesh_emit(const Table& T, const Pool& Pl, const Table& H, const Pool& HP,
                             const uint64_t* d_keys, uint32_t nb, float min_weight, int tab,
                             float vs, const uint64_t* d_offsets, float* d_tri, hipStream_t st);
+// indexed mesh (tsdf_mesh.hip; include/tsdf_hip_mesh.h; the box and the brick list: mesh_plan.h).
+// d_keys: the nb listed bricks, sorted; d_mask: MESH_VMASK_WORDS words per listed brick (zeroed
+// here), bit 3 l + axis = the edge from in-brick voxel l along axis carries a vertex; d_tcnt /
+// d_vcnt: triangles and vertices per listed brick; d_slot_idx: n_pool words (the map's bricks),
+// filled here with the list position of every pool slot
+struct MeshBox;
+constexpr int MESH_VMASK_WORDS = 3 * BRICK_VOX / 32;
+hipError_t launch_mesh_mark(const Table& T, const Pool& Pl, const uint64_t* d_keys, uint32_t nb,
+                            float min_weight, int tab, const MeshBox& B, uint32_t n_pool,
+                            uint32_t* d_slot_idx, uint32_t* d_mask, uint32_t* d_tcnt,
+                            uint32_t* d_vcnt, hipStream_t st);
+// d_toff / d_vbase: the exclusive prefixes of d_tcnt / d_vcnt; d_vert and d_nrm (may be null)
+// 3 floats per vertex, d_tri 3 indices per triangle
+hipError_t launch_mesh_fill(const Table& T, const Pool& Pl, const uint64_t* d_keys, uint32_t nb,
+                            float min_weight, int tab, const MeshBox& B, float vs, float inv,
+                            uint32_t n_pool, const uint32_t* d_slot_idx, const uint32_t* d_mask,
+                            const uint32_t* d_tcnt, const uint32_t* d_vcnt,
+                            const uint64_t* d_toff, const uint32_t* d_vbase, float* d_vert,
+                            float* d_nrm, uint32_t* d_tri, hipStream_t st);
 // sparse map queries (tsdf_sample.hip; include/tsdf_hip_sample.h)
 // mode: TSDF_SAMPLE_NEAREST / TSDF_SAMPLE_TRILINEAR; d_grad may be null; any n (the grid strides)
 hipError_t launch_sample(const Table& T, const Pool& Pl, const RayConst& R, const float* d_xyz,

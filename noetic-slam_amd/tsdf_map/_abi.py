@@ -235,6 +235,27 @@ MERGE_SIGNATURES = {
 }
 
 
+# include/tsdf_hip_mesh.h (TSDF_MESH_API): the indexed triangle mesh (shared vertices, normals, a
+# voxel box), likewise a feature of libtsdf_hip.so outside the contract, declared on the HIP
+# library only.  Tables: MC_TABLES.
+class MeshCounts(C.Structure):
+    """tsdf_mesh_counts (include/tsdf_hip_mesh.h)."""
+    _fields_ = [("n_bricks", C.c_uint64), ("n_vertices", C.c_uint64), ("n_triangles", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+U32P = C.POINTER(C.c_uint32)
+MESH_SIGNATURES = {
+    "tsdf_mesh_indexed_count": (C.c_int, [P, C.c_float, C.c_int32, L3, L3, C.POINTER(MeshCounts)]),
+    "tsdf_mesh_indexed": (C.c_int, [P, C.c_float, C.c_int32, L3, L3, FP, FP, U32P, C.c_uint64,
+                                    C.c_uint64, C.POINTER(MeshCounts)]),
+    "tsdf_mesh_indexed_device": (C.c_int, [P, C.c_float, C.c_int32, L3, L3, P, P, P, C.c_uint64,
+                                           C.c_uint64, C.POINTER(MeshCounts)]),
+}
+
+
 def declare(lib, names=None, optional=(), table=None):
     """Attach restype/argtypes for the ABI symbols present in `lib`; raise if a required one is
     missing.  table: the signature table (default SIGNATURES, the tsdf_hip.h contract)."""

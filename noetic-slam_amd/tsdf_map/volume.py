@@ -388,7 +388,8 @@ class TSDFVolume:
         with an unobserved voxel are never meshed.  table: "generated" (face-consistent, the
         default) or "lorensen" (the published Lorensen / Bourke table, VDBFusion's).
         halo: (d_tiles_ptr, n_tiles) of neighbour bricks another rank owns (tsdf_extract_mesh_halo,
-        in `tensor_device` memory): after a border reduce each rank meshes its own cubes."""
+        in `tensor_device` memory): after a border reduce each rank meshes its own cubes.
+        `extract_indexed_mesh` returns the same triangles with shared vertices and normals."""
         tab = _abi.MC_TABLES[table]
         n = C.c_uint64()
 
@@ -405,6 +406,63 @@ class TSDFVolume:
         if n.value:
             self._check(call(t.ctypes.data_as(_abi.FP), n.value), "extract_mesh")
         return t.reshape(-1, 3), np.arange(3 * t.shape[0], dtype=np.int64).reshape(-1, 3)
+
+    # -- indexed mesh (include/tsdf_hip_mesh.h) --------------------------------------------------
+    def _mesh_fn(self, name):
+        """An entry point of include/tsdf_hip_mesh.h, detected by the symbol like `_sample_fn`."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (the indexed mesh is part of "
+                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    @staticmethod
+    def _mesh_box(lo, hi):
+        """(lo, hi) as int64[3] arrays with their ctypes pointers, or Nones for the whole map."""
+        if lo is None and hi is None:
+            return None, None, None, None
+        if lo is None or hi is None:
+            raise ValueError("lo and hi must both be given or both be None")
+        lo = np.ascontiguousarray(np.asarray(lo, np.int64).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(hi, np.int64).reshape(3))
+        return lo, hi, lo.ctypes.data_as(_abi.L3), hi.ctypes.data_as(_abi.L3)
+
+    def indexed_mesh_counts(self, min_weight=0.0, table="generated", lo=None, hi=None):
+        """tsdf_mesh_indexed_count: {"n_bricks", "n_vertices", "n_triangles"} of the mesh that
+        `extract_indexed_mesh` would return."""
+        fn = self._mesh_fn("tsdf_mesh_indexed_count")
+        lo, hi, plo, phi = self._mesh_box(lo, hi)
+        st = _abi.MeshCounts()
+        self._check(fn(self._ctx, float(min_weight), _abi.MC_TABLES[table], plo, phi,
+                       C.byref(st)), "indexed_mesh_counts")
+        return st.as_dict()
+
+    def extract_indexed_mesh(self, min_weight=0.0, table="generated", lo=None, hi=None,
+                             normals=True):
+        """The marching-cubes mesh with shared vertices: (vertices (V, 3) float32, triangles
+        (T, 3) uint32, normals (V, 3) float32 or None).  One vertex per grid edge the surface
+        crosses; `vertices[triangles]` is `extract_triangle_mesh`'s soup bit for bit, in its
+        order.  Normals are the field's gradient at the vertex, unit length, pointing out of the
+        surface.  lo / hi: mesh only the cubes whose min voxel lies in the voxel box [lo, hi)
+        (`mesh.mesh_tiles` walks a map in such boxes).  include/tsdf_hip_mesh.h states the rules."""
+        fn = self._mesh_fn("tsdf_mesh_indexed")
+        tab = _abi.MC_TABLES[table]
+        lo, hi, plo, phi = self._mesh_box(lo, hi)
+        st = _abi.MeshCounts()
+        for _ in range(2):
+            n = self.indexed_mesh_counts(min_weight, table, lo, hi)
+            v = np.empty((n["n_vertices"], 3), np.float32)
+            t = np.empty((n["n_triangles"], 3), np.uint32)
+            nr = np.empty_like(v) if normals else None
+            rc = fn(self._ctx, float(min_weight), tab, plo, phi, v.ctypes.data_as(_abi.FP),
+                    nr.ctypes.data_as(_abi.FP) if normals else None,
+                    t.ctypes.data_as(_abi.U32P), v.shape[0], t.shape[0], C.byref(st))
+            if rc == _abi.TSDF_EOVERFLOW:
+                continue
+            self._check(rc, "extract_indexed_mesh")
+            nv, nt = st.n_vertices, st.n_triangles
+            return v[:nv], t[:nt], (nr[:nv] if normals else None)
+        raise TsdfError(_abi.TSDF_EOVERFLOW, "extract_indexed_mesh: the mesh kept changing")
 
     def num_bricks(self):
         n = C.c_uint64()
@@ -428,6 +486,20 @@ class TSDFVolume:
             k = n_out.value
             return coords[:k], s[:k], w[:k]
         raise TsdfError(_abi.TSDF_EOVERFLOW, "export_bricks: brick count kept changing")
+
+    def brick_coords(self):
+        """The map's brick coordinates (nb, 3) int32 in (z, y, x) order, without the voxels."""
+        for _ in range(2):
+            nb = self.num_bricks()
+            coords = np.empty((nb, 3), np.int32)
+            n_out = C.c_uint64()
+            rc = self._lib.tsdf_export_bricks(self._ctx, coords.ctypes.data_as(_abi.I3), None,
+                                              None, nb, C.byref(n_out))
+            if rc == _abi.TSDF_EOVERFLOW:
+                continue
+            self._check(rc, "brick_coords")
+            return coords[:n_out.value]
+        raise TsdfError(_abi.TSDF_EOVERFLOW, "brick_coords: brick count kept changing")
 
     def import_bricks(self, coords, sdf, weight):
         coords = np.ascontiguousarray(coords, np.int32).reshape(-1, 3)
@@ -817,6 +889,33 @@ class HipTSDFVolume(TSDFVolume):
                        band, float(min_weight), C.c_void_p(dist.data_ptr()),
                        C.c_void_p(fl.data_ptr() if flags else 0)), "esdf_device")
         return dist, fl
+
+    def indexed_mesh_device(self, min_weight=0.0, table="generated", lo=None, hi=None,
+                            normals=True):
+        """`extract_indexed_mesh` into device tensors on the volume's GPU: (vertices (V, 3)
+        float32, triangles (T, 3) uint32, normals (V, 3) float32 or None), complete when the call
+        returns."""
+        import torch
+        fn = self._mesh_fn("tsdf_mesh_indexed_device")
+        tab = _abi.MC_TABLES[table]
+        lo, hi, plo, phi = self._mesh_box(lo, hi)
+        st = _abi.MeshCounts()
+        for _ in range(2):
+            n = self.indexed_mesh_counts(min_weight, table, lo, hi)
+            nv, nt = n["n_vertices"], n["n_triangles"]
+            v = torch.empty((nv, 3), dtype=torch.float32, device=self.tensor_device)
+            t = torch.empty((nt, 3), dtype=torch.uint32, device=self.tensor_device)
+            nr = torch.empty_like(v) if normals else None
+            torch.cuda.synchronize(v.device)
+            rc = fn(self._ctx, float(min_weight), tab, plo, phi, C.c_void_p(v.data_ptr()),
+                    C.c_void_p(nr.data_ptr() if normals else 0), C.c_void_p(t.data_ptr()), nv, nt,
+                    C.byref(st))
+            if rc == _abi.TSDF_EOVERFLOW:
+                continue
+            self._check(rc, "indexed_mesh_device")
+            nv, nt = st.n_vertices, st.n_triangles
+            return v[:nv], t[:nt], (nr[:nv] if normals else None)
+        raise TsdfError(_abi.TSDF_EOVERFLOW, "indexed_mesh_device: the mesh kept changing")
 
     def align_terms(self, points, pose, min_weight=0.0, n=None):
         """Gauss-Newton terms of the point-to-TSDF error of a cloud under `pose` (3x4 or 4x4, world
