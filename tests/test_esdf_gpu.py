@@ -1,13 +1,14 @@
 """The distance field on the GPU (include/tsdf_hip_esdf.h) against tests/esdfref.py, bit for bit:
 dist as uint32, flags as uint8.  The reference reads the GPU volume's own query_dense, so what
 test_esdf_ref.py pins on the CPU is what the kernels are held to here.  No box has more than about
-3 * 10^5 voxels."""
+3 * 10^5 voxels, but the three of tests/pastcap.py, which take each kernel past its grid cap."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import esdfref as er
+import pastcap as pc
 import sampleref as sr
 
 pytestmark = pytest.mark.gpu
@@ -140,6 +141,24 @@ def synthetic(voxels, sem="vdbfusion_f64"):
     if voxels:
         v.import_bricks(*er.make_bricks(voxels, 0.0 if sem == "voxblox" else F(TAU)))
     return v
+
+
+@pytest.mark.parametrize("name", list(pc.ESDF_BOXES))
+def test_past_the_grid_cap(name):
+    """Thin boxes with more tiles than ESDF_GRID_CAP in one or two passes: the voxels of the later
+    trips hold seeded sites and uncapped voxels, on either side of the trip's boundary."""
+    voxels, lo, hi, radius, (S, W), ref = pc.esdf_case(name)
+    sides = pc.esdf_sides(name)
+    print("%s %s R %d: %s" % (name, tuple((hi - lo).tolist()), radius,
+                              {k: d["tiles"] for k, d in sides.items()}))
+    for kernel in pc.ESDF_BOXES[name]["past"]:
+        print("  %s: %s" % (kernel, sides[kernel]))
+    pc.assert_esdf_past_cap(name, sides)
+    v = synthetic(voxels)
+    gs, gw = v.query_dense(lo, hi)  # the volume holds the field the reference was computed on
+    assert np.array_equal(er.bits(gs), er.bits(S)) and np.array_equal(er.bits(gw), er.bits(W))
+    check_box(v, lo, hi, radius, ref=ref)
+    v.close()
 
 
 def test_single_site_in_a_brick_corner():

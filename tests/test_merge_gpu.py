@@ -2,7 +2,9 @@
 tests/mergeref.py, bit for bit: export_bricks() of the destination as uint32, the set of brick
 coordinates included (an empty brick left behind fails), and the four counts of the contract.  The
 reference enumerates the destination voxels generously and never sees the library's candidate
-list.  Source maps are one scan cropped to a box of bricks, so the numpy reference is instant."""
+list.  Source maps are one scan cropped to a box of bricks, so the numpy reference is instant; the
+uncropped map, whose candidates outnumber the per-brick kernels' grid cap, is merged in four cases
+(tests/pastcap.py)."""
 import ctypes as C
 
 import numpy as np
@@ -10,6 +12,7 @@ import pytest
 
 import mergeref as mr
 import oracle
+import pastcap as pc
 import sampleref as sr
 
 pytestmark = pytest.mark.gpu
@@ -389,10 +392,45 @@ def test_equals_sample_then_import_on_the_uncropped_map(maps, mode):
     route.import_bricks(*bricks_of(v[valid], s[valid], w[valid], F(TAU)))
     dst = hip()
     st = dst.merge_from(src, T, mode=mode)
+    assert st["candidate_bricks"] > pc.MERGE_CAP
     assert st["merged_voxels"] == int(valid.sum()) and st["new_bricks"] == route.num_bricks()
     mr.assert_same_bricks(dst.export_bricks(), route.export_bricks())
     for x in (src, route, dst):
         x.close()
+
+
+# ---- more candidate bricks than the grid cap, against the numpy reference ------------------------
+
+@pytest.fixture(scope="module")
+def full_source(maps):
+    """The uncropped scan-0 map as a volume (8693 bricks) and its export_voxels()."""
+    src = hip()
+    src.import_bricks(*maps["vdbfusion_f64"]["full"])
+    yield src, src.export_voxels()
+    src.close()
+
+
+@pytest.mark.parametrize("mode", MODES)
+@pytest.mark.parametrize("case", list(pc.MERGE_CASES))
+def test_past_the_grid_cap(maps, full_source, case, mode):
+    """k_merge_flag and k_merge_apply take one candidate brick per workgroup, 8192 workgroups at
+    the most.  Into an empty map under the general pose; and into a map that holds every second
+    brick of the source under the half-voxel shift, where held and new candidates alternate and
+    the slot a workgroup hands round in LDS changes from trip to trip."""
+    full = maps["vdbfusion_f64"]["full"]
+    src, voxels = full_source
+    pose = pc.MERGE_CASES[case][0]
+    assert np.array_equal(pose, POSES["general" if case == "empty_general" else "half_voxel"])
+    dst = hip(max_bricks=1 << 15)
+    held = pc.merge_destination(full, case)
+    if held[0].shape[0]:
+        dst.import_bricks(*held)
+    exp, st = merge_and_check(dst, src, pose, mode, src_voxels=voxels)
+    print("%s %s: %s" % (case, mode, st))
+    # the candidate list is what tests/test_merge_plan.py's restated search lists
+    assert st["candidate_bricks"] == pc.merge_candidates(full[0], pose, mode) > pc.MERGE_CAP
+    pc.assert_merge_past_cap(case, st["candidate_bricks"], exp.counts)
+    dst.close()
 
 
 # ---- the merged map is a map like any other ------------------------------------------------------
@@ -415,8 +453,8 @@ def test_a_scan_integrated_after_the_merge_is_the_oracles(maps, sim, pipeline):
 
 
 def test_queries_read_the_merged_field(maps, scan0):
-    """sample, raycast, esdf and the mesh after a merge, each against its own reference run on the
-    merged map's export."""
+    """sample, raycast, esdf and both meshes after a merge, each against its own reference run on
+    the merged map's export."""
     from test_prune_gpu import cut_box
     from test_queries_after_change_gpu import Refs, check
     m = maps["vdbfusion_f64"]
@@ -434,7 +472,7 @@ def test_queries_read_the_merged_field(maps, scan0):
     # the change shows in the queries: some samples differ from the map before the merge
     s0 = sr.sample(before, refs.queries, sr.TRILINEAR)[0]
     assert (refs.get("sample", "trilinear")[0] != s0).sum() >= 100
-    check(dst, refs, twin, kinds=("sample", "raycast", "esdf", "mesh"))
+    check(dst, refs, twin, kinds=("sample", "raycast", "esdf", "mesh", "imesh"))
     dst.close()
     twin.close()
 

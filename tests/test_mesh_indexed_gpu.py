@@ -1,13 +1,15 @@
 """The indexed mesh on the GPU (include/tsdf_hip_mesh.h): vertices, normals and triangles equal
 tests/meshref.py bit for bit, and de-indexed they are the GPU's own soup, on a sphere, a field with
 holes and low weights, a missing neighbour brick, an integrated scan and boxes that cut bricks; the
-capacity protocol, the device outputs, the refusals, and independence of the pool's order."""
+capacity protocol, the device outputs, the refusals, and independence of the pool's order; and a
+sphere of more bricks than the per-brick kernels' grid cap (tests/pastcap.py)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
 import meshref
+import pastcap as pc
 from test_mesh import TAU, VS, sphere_bricks
 from tsdf_map import HipTSDFVolume, _abi, load_hip_library
 from tsdf_map.mesh import mesh_tiles, tile_boxes
@@ -18,6 +20,7 @@ SMALL = dict(max_bricks=1 << 12, max_points=1 << 13, max_batch=4)
 # the surface crosses the brick faces at voxel 0 on every axis, at -8 on y and at +8 on x and z
 CENTER = (0.113, -0.121, 0.207)
 TABLES = ["generated", "lorensen"]
+VOXBLOX_MIN_WEIGHT = 1.5  # between one observation (W <= 1) and two
 
 
 def u32(a):
@@ -112,26 +115,41 @@ def test_missing_neighbour_brick(sphere):
     g.close()
 
 
-def test_integrated_scan(sim):
+def integrated_scan(sim, semantics, min_weights, **kw):
     """A few thousand rays of one generated scan: the reference from query_dense of the touched
     box."""
     pts, org = sim.scan(0)
     vs = 0.1
-    g = HipTSDFVolume(vs, 3 * vs, **SMALL)
+    g = HipTSDFVolume(vs, 3 * vs, semantics=semantics, **dict(SMALL, **kw))
     g.integrate(np.ascontiguousarray(pts[20000:20000 + 6144]), org)
     c = g.brick_coords()
     assert 50 < c.shape[0] < 1000
     lo, hi = c.min(0).astype(np.int64) * 8 - 2, (c.max(0).astype(np.int64) + 1) * 8 + 2
     S, W = g.query_dense(lo, hi)
     tab = table("generated")
-    for mw in (0.0, 2.0):
+    for mw in min_weights:
         ref = meshref.indexed_mesh_ref(S, W, lo, vs, tab, min_weight=mw)
+        print("%s min_weight %g: %d vertices, %d triangles" % (semantics, mw, ref[0].shape[0],
+                                                               ref[2].shape[0]))
         assert ref[2].shape[0] > (1000 if mw == 0.0 else 50)
         got = g.extract_indexed_mesh(min_weight=mw)
         same_mesh(got, ref)
         soup, _ = g.extract_triangle_mesh(min_weight=mw)
         assert np.array_equal(u32(meshref.deindex(got[0], got[1])), u32(soup))
     g.close()
+    return W
+
+
+def test_integrated_scan(sim):
+    integrated_scan(sim, "vdbfusion_f64", (0.0, 2.0))
+
+
+def test_integrated_scan_voxblox(sim):
+    """The same in the Voxblox semantics: background 0, and weights that drop off behind the
+    surface, so that a min_weight of 1.5 removes about three quarters of the observed voxels."""
+    W = integrated_scan(sim, "voxblox", (0.0, VOXBLOX_MIN_WEIGHT), max_range=40.0)
+    seen = W[W > 0]
+    assert (seen < VOXBLOX_MIN_WEIGHT).sum() >= 1000 and (seen >= VOXBLOX_MIN_WEIGHT).sum() >= 1000
 
 
 def test_box_partition(sphere):
@@ -316,3 +334,109 @@ def test_pool_order(holed):
         got = h.extract_indexed_mesh(min_weight=0.75)
         same_mesh(got, (want[0], want[2], want[1]))
         h.close()
+
+
+# ---- more bricks than the grid cap ---------------------------------------------------------------
+
+LARGE = dict(max_bricks=1 << 13)
+
+
+@pytest.fixture(scope="module")
+def large():
+    """kind -> volume of the 18^3-brick sphere (tests/pastcap.py); the tests only read."""
+    out = {kind: volume(pc.mesh_map(kind), **LARGE) for kind in ("full", "holed")}
+    yield out
+    for g in out.values():
+        g.close()
+
+
+def check_large(g, kind, tname, min_weight, boxed):
+    """The volume's mesh against pastcap's reference of the same case, whose conditions are
+    asserted again; returns the volume's mesh."""
+    assert np.array_equal(table(tname), pc.mc_table(tname))
+    ref, sides = pc.mesh_case(kind, tname, min_weight, boxed)
+    print("%s %s min_weight %g %s: %s" % (kind, tname, min_weight, "box" if boxed else "whole",
+                                          sides))
+    pc.assert_mesh_past_cap(sides)
+    lo, hi = pc.MESH_BOX if boxed else (None, None)
+    got = g.extract_indexed_mesh(min_weight=min_weight, table=tname, lo=lo, hi=hi)
+    same_mesh(got, ref)
+    # (n_bricks counts the bricks that hold a voxel of the box; the kernels also list the owners
+    # of the vertices on its high faces, which sides["n_bricks"] counts)
+    examined = pc.mesh_listed(pc.mesh_map(kind)[0], lo, hi - 1).shape[0] if boxed else \
+        sides["n_bricks"]
+    cnt = g.indexed_mesh_counts(min_weight=min_weight, table=tname, lo=lo, hi=hi)
+    assert cnt == {"n_bricks": examined, "n_vertices": sides["n_vertices"],
+                   "n_triangles": sides["n_triangles"]}
+    return got
+
+
+@pytest.mark.parametrize("kind,tname,min_weight", [("full", "generated", 0.0),
+                                                   ("holed", "lorensen", 0.75)])
+def test_past_the_grid_cap(large, kind, tname, min_weight):
+    """5832 bricks against the cap of 4096 workgroups: the bricks from (1, 2, 3) on are meshed on
+    a workgroup's second trip, and the triangles around z = 24 index vertices of both trips."""
+    g = large[kind]
+    v, t, n = check_large(g, kind, tname, min_weight, False)
+    soup, _ = g.extract_triangle_mesh(min_weight=min_weight, table=tname)
+    assert np.array_equal(u32(meshref.deindex(v, t)), u32(soup))
+    if kind == "full":
+        assert np.unique(t).shape[0] == v.shape[0] and v.shape[0] * 2 - 4 == t.shape[0]  # closed
+
+
+def test_box_past_the_grid_cap(large):
+    """A box that cuts bricks and lists 4860 of them, more than the cap."""
+    g = large["full"]
+    v, t, n = check_large(g, "full", "generated", 0.0, True)
+    assert 0 < t.shape[0] < g.indexed_mesh_counts()["n_triangles"]
+
+
+def test_device_outputs_past_the_grid_cap(large):
+    g = large["full"]
+    ref, sides = pc.mesh_case("full", "generated", 0.0, False)
+    pc.assert_mesh_past_cap(sides)
+    dv, dt, dn = g.indexed_mesh_device()
+    same_mesh((dv.cpu().numpy(), dt.cpu().numpy(), dn.cpu().numpy()), ref)
+    hv, ht, hn = g.extract_indexed_mesh()
+    same_mesh((dv.cpu().numpy(), dt.cpu().numpy(), dn.cpu().numpy()), (hv, hn, ht))
+
+
+def test_pool_order_past_the_grid_cap():
+    """The bricks imported in reverse order behind a decoy that is then evicted: every brick's
+    pool slot differs from its position in the sorted list, before the cap and past it."""
+    c, s, w = pc.mesh_map("full")
+    assert np.array_equal(c, pc.mesh_listed(c))  # (z, y, x) order: position = row
+    h = HipTSDFVolume(VS, TAU, **dict(SMALL, **LARGE))
+    h.import_bricks(np.array([[500, 500, 500]], np.int32), s[:1], w[:1])
+    h.import_bricks(c[::-1], s[::-1], w[::-1])
+    assert h.evict_outside((-400, -400, -400), (400, 400, 400), copy_out=False) == 1
+    assert h.num_bricks() == c.shape[0] > pc.MESH_CAP
+    check_large(h, "full", "generated", 0.0, False)
+    h.close()
+
+
+def test_vertex_counts_past_their_grid_cap():
+    """k_mesh_vcount takes four bricks a workgroup, so its second trip starts at brick 16 384: a
+    sphere of 26^3 bricks.  No numpy reference at this size; a wrong count moves every later
+    brick's first vertex, so the de-indexed mesh is held to the GPU's own soup, and the surface
+    is closed."""
+    sides = pc.mesh_big_sides()
+    print("26^3 bricks: %s" % sides)
+    pc.assert_mesh_vcount_past_cap(sides)
+    g = volume(pc.mesh_big_map(), max_bricks=1 << 15)
+    v, t, n = g.extract_indexed_mesh()
+    soup, _ = g.extract_triangle_mesh()
+    assert t.shape[0] * 3 == soup.shape[0] > 0
+    assert np.array_equal(u32(meshref.deindex(v, t)), u32(soup))
+    assert int(t.max()) + 1 == v.shape[0] == np.unique(t).shape[0]
+    assert v.shape[0] * 2 - 4 == t.shape[0]  # closed
+    nn = np.linalg.norm(n.astype(np.float64), axis=1)
+    assert np.all((np.abs(nn - 1) < 1e-6) | (nn == 0)) and (nn > 0).mean() > 0.99
+    assert g.indexed_mesh_counts() == {"n_bricks": sides["n_bricks"], "n_vertices": v.shape[0],
+                                       "n_triangles": t.shape[0]}
+    # the vertices of the last bricks, which the later trips counted, lie on the sphere's top
+    top = v[v[:, 2] >= np.float32(88.5) * np.float32(VS)]
+    assert top.shape[0] >= sides["vertices_past"]
+    r = np.linalg.norm(top.astype(np.float64) - np.array(pc.MESH_BIG_CENTER), axis=1)
+    assert np.all(np.abs(r - pc.MESH_BIG_RADIUS) < VS)
+    g.close()

@@ -6,7 +6,9 @@ with batches still queued.  A stale slot, a key the rehash left behind or a poin
 growth shows first in the queries, so after each change the GPU's export must equal the oracle
 twin's (the change applied to the oracle the way tests/test_prune_gpu.py does), and then sample,
 align_terms, raycast, esdf and query_dense must equal the numpy references run on that export, bit
-for bit, and the mesh the twin's.
+for bit, and the mesh the twin's.  The indexed mesh, the one query with a slot map of its own (pool
+slot -> position in the sorted brick list), de-indexed must be that soup, and in the probes' box it
+must equal tests/meshref.py on the export.
 
 For the changes that remove something the same references run on the map before the change, and
 the test asserts that the change shows in them (queries, rays and distance-field sites lost)."""
@@ -14,6 +16,7 @@ import numpy as np
 import pytest
 
 import esdfref
+import meshref
 import rayref as rr
 import sampleref as sr
 from conftest import decimate
@@ -27,17 +30,22 @@ BASE = dict(voxel_size=sr.VOXEL_SIZE, sdf_trunc=sr.SDF_TRUNC)
 MODES = {"nearest": sr.NEAREST, "trilinear": sr.TRILINEAR}
 RADIUS = 12                    # voxels: the distance field is exact up to 1.2 m
 T_MIN, T_MAX, STEP = rr.T_MIN, rr.T_MAX, rr.STEP  # 0.5 .. 40 m every 0.05 m
-KINDS = ("sample", "align", "raycast", "esdf", "dense", "mesh")
+KINDS = ("sample", "align", "raycast", "esdf", "dense", "mesh", "imesh")
+MESH_MARGIN = 2                # voxels of field around the box that the mesh reference reads
 
 
 def kw_of(semantics="vdbfusion_f64", **kw):
     return sem_kw(semantics, **dict(BASE, **kw))
 
 
-@pytest.fixture(scope="module")
-def scans(sim):
+def decimated_scans(sim):
     """Scans 0..5 of the trajectory, every fourth point."""
     return [(decimate(p, 4), o) for p, o in (sim.scan(k) for k in range(6))]
+
+
+@pytest.fixture(scope="module")
+def scans(sim):
+    return decimated_scans(sim)
 
 
 @pytest.fixture(scope="module")
@@ -109,6 +117,14 @@ class Refs:
                 S, W = self.get("dense")
                 r = esdfref.esdf(S, W, self.vs, RADIUS, self.vs) + (
                     esdfref.classify(S, W, self.vs, 0.0)[1],)
+            elif kind == "imesh":  # (vertices, normals, triangles) of the cubes in the box
+                import oracle
+                from tsdf_map import _abi
+                lo, hi = self.box
+                S, W = dense_of(self.field, lo - MESH_MARGIN, hi + MESH_MARGIN)
+                # (the oracle's table: tests/test_mesh.py holds the library's to it)
+                tab = meshref.mc_table(oracle.load(), _abi.MC_TABLES["generated"])
+                r = meshref.indexed_mesh_ref(S, W, lo - MESH_MARGIN, self.vs, tab, lo=lo, hi=hi)
             self.memo[k] = r
         return self.memo[k]
 
@@ -152,6 +168,20 @@ def check(g, refs, twin, kinds=KINDS):
             vg, _ = g.extract_triangle_mesh()
             vo, _ = twin.extract_triangle_mesh()
             assert len(vo) >= 300 and vg.shape == vo.shape and np.array_equal(bits(vg), bits(vo))
+        elif kind == "imesh":
+            v, t, n = g.extract_indexed_mesh()
+            vo, _ = twin.extract_triangle_mesh()
+            soup = meshref.deindex(v, t)
+            assert len(vo) >= 300 and soup.shape == vo.shape and np.array_equal(bits(soup), bits(vo))
+            assert int(t.max()) + 1 == len(v) == np.unique(t).size
+            assert g.indexed_mesh_counts() == {"n_bricks": g.num_bricks(), "n_vertices": len(v),
+                                               "n_triangles": len(t)}
+            rv, rn, rt = refs.get("imesh")
+            assert len(rt) >= 50, len(rt)
+            bv, bt, bn = g.extract_indexed_mesh(lo=refs.box[0], hi=refs.box[1])
+            assert bt.shape == rt.shape and np.array_equal(bt, rt)
+            assert bv.shape == rv.shape and np.array_equal(bits(bv), bits(rv))
+            assert np.array_equal(bits(bn), bits(rn))
 
 
 def counts(refs):
@@ -160,6 +190,7 @@ def counts(refs):
     out.update({"hits_" + m: int(refs.get("raycast", m)[2].sum()) for m in MODES})
     out["n_valid_align"] = refs.get("align")[3]
     out["sites"] = int(refs.get("esdf")[2].sum())
+    out["box_triangles"] = int(refs.get("imesh")[2].shape[0])
     out["observed"] = int((refs.get("dense")[1] > 0).sum())
     return out
 
@@ -170,6 +201,7 @@ def assert_not_vacuous(c):
     for m in MODES:  # (trilinear hits need two fully observed cubes in a row: rare after a prune)
         assert c["valid_" + m] >= 100 and c["hits_" + m] >= (100 if m == "nearest" else 10), c
     assert c["n_valid_align"] >= 100 and c["sites"] >= 100 and c["observed"] >= 1000, c
+    assert c["box_triangles"] >= 50, c
 
 
 def assert_change_shows(before, after):
@@ -190,14 +222,78 @@ def assert_change_shows(before, after):
     return out
 
 
+def build_twin(scans, **kw):
+    """The oracle volume after the scans."""
+    o = ora(**kw)
+    for pts, org in scans:
+        o.integrate(pts, org)
+    return o
+
+
 def build(scans, **kw):
     """(GPU volume, oracle twin) after the same scans; the fields are equal before any change."""
-    g, o = hip(**kw), ora(**kw)
+    g, o = hip(**kw), build_twin(scans, **kw)
     for pts, org in scans:
         g.integrate(pts, org)
-        o.integrate(pts, org)
     assert bitwise(g, o)
     return g, o
+
+
+# The changes as the oracle twin sees them.  The tests below apply the same boxes, thresholds and
+# parts to the GPU volume; tests/test_pastcap_inputs.py builds the twins alone, on the CPU.
+
+def evicted_twin(o, **kw):
+    """(twin, (lo, hi)): o without the bricks outside cut_box."""
+    lo, hi = cut_box(o.export_bricks()[0])
+    return reference(o, lambda c: inside(c, lo, hi), **kw), (lo, hi)
+
+
+def import_part(second, cut):
+    """The bricks of the export `second` inside the brick box `cut`."""
+    return rows(second, inside(second[0], *cut))
+
+
+def second_evict_box(c0):
+    """The other box of evict-integrate-evict: everything from the median brick y on goes."""
+    c0 = np.asarray(c0, np.int64)
+    lo2, hi2 = c0.min(0), c0.max(0) + 1
+    hi2[1] = int(np.median(c0[:, 1]))
+    return lo2, hi2
+
+
+def evict_integrate_evict_twins(o, again, **kw):
+    """(twin after evict and the scans `again`, twin after the second evict, first box, second
+    box)."""
+    c0 = o.export_bricks()[0]
+    lo, hi = cut_box(c0)
+    o2 = reference(o, lambda c: inside(c, lo, hi), again, **kw)
+    lo2, hi2 = second_evict_box(c0)
+    return o2, reference(o2, lambda c: inside(c, lo2, hi2), **kw), (lo, hi), (lo2, hi2)
+
+
+PRUNE_WEIGHT = 2.0
+
+
+def twins(scans):
+    """name -> (oracle twin, cut) of every map the tests below query."""
+    out = {}
+    for sem in ("vdbfusion_f64", "voxblox"):
+        kw = kw_of(sem)
+        out["evict " + sem] = evicted_twin(build_twin(scans[:4], **kw), **kw)
+    kw = kw_of()
+    o = build_twin(scans[:4], **kw)
+    cut = cut_box(o.export_bricks()[0])
+    out["growth"] = (o, cut)
+    out["prune"] = (pruned_twin(o, PRUNE_WEIGHT, **kw)[0], cut)
+    o6 = build_twin(scans, **kw)
+    out["pipelined"] = (o6, cut_box(o6.export_bricks()[0]))
+    a, b = build_twin(scans[:2], **kw), build_twin(scans[2:4], **kw)
+    cut = cut_box(a.export_bricks()[0].astype(np.int64))
+    a.import_bricks(*import_part(b.export_bricks(), cut))
+    out["import"] = (a, cut)
+    _, twin, first, _ = evict_integrate_evict_twins(o, scans[4:6], **kw)
+    out["evict, integrate, evict"] = (twin, first)
+    return out
 
 
 def pruned_twin(o, m, **kw):
@@ -219,11 +315,10 @@ def pruned_twin(o, m, **kw):
 def test_after_evict(scans, probes, semantics):
     kw = kw_of(semantics)
     g, o = build(scans[:4], **kw)
-    lo, hi = cut_box(o.export_bricks()[0])
+    twin, (lo, hi) = evicted_twin(o, **kw)
     n0 = g.num_bricks()
     n_ev = g.evict_outside(lo, hi, copy_out=False)
     assert 0 < n_ev < n0 and g.num_bricks() == n0 - n_ev
-    twin = reference(o, lambda c: inside(c, lo, hi), **kw)
     assert bitwise(g, twin)
     after = Refs(g, (lo, hi), probes)
     shows = assert_change_shows(Refs(o, (lo, hi), probes), after)
@@ -238,8 +333,8 @@ def test_after_prune(scans, probes):
     kw = kw_of()
     g, o = build(scans[:4], **kw)
     cut = cut_box(o.export_bricks()[0])
-    twin, n_gone = pruned_twin(o, 2.0, **kw)
-    assert g.prune(2.0) == n_gone
+    twin, n_gone = pruned_twin(o, PRUNE_WEIGHT, **kw)
+    assert g.prune(PRUNE_WEIGHT) == n_gone
     assert bitwise(g, twin)
     after = Refs(g, cut, probes)
     shows = assert_change_shows(Refs(o, cut, probes), after)
@@ -273,8 +368,7 @@ def test_after_import_merge(scans, probes):
     g2, o2 = build(scans[2:4], **kw)
     held = o.export_bricks()[0].astype(np.int64)
     cut = cut_box(held)
-    part = g2.export_bricks()
-    part = rows(part, inside(part[0], *cut))
+    part = import_part(g2.export_bricks(), cut)
     new = part[0].astype(np.int64)
     key = lambda c: (c[:, 0] + (1 << 20)) | ((c[:, 1] + (1 << 20)) << 21) | ((c[:, 2] + (1 << 20)) << 42)  # noqa: E731
     share, fresh = np.isin(key(held), key(new)).mean(), int((~np.isin(key(new), key(held))).sum())
@@ -283,8 +377,7 @@ def test_after_import_merge(scans, probes):
     assert 0.3 <= share <= 0.7 and fresh >= 10
     before = o.export_voxels()
     g.import_bricks(*part)
-    opart = o2.export_bricks()
-    o.import_bricks(*rows(opart, inside(opart[0], *cut)))
+    o.import_bricks(*import_part(o2.export_bricks(), cut))
     assert bitwise(g, o) and not same_voxels(before, o.export_voxels())
     refs = Refs(g, cut, probes)
     assert_not_vacuous(counts(refs))
@@ -297,21 +390,15 @@ def test_after_evict_integrate_evict(scans, probes):
     """Evict, integrate two more scans back into the removed region, evict with another box."""
     kw = kw_of()
     g, o = build(scans[:4], **kw)
-    c0 = o.export_bricks()[0]
-    lo, hi = cut_box(c0)
-    assert g.evict_outside(lo, hi, copy_out=False) > 0
     again = scans[4:6]
+    o2, twin, (lo, hi), (lo2, hi2) = evict_integrate_evict_twins(o, again, **kw)
+    assert g.evict_outside(lo, hi, copy_out=False) > 0
     for pts, org in again:
         g.integrate(pts, org)
-    o2 = reference(o, lambda c: inside(c, lo, hi), again, **kw)
     assert bitwise(g, o2) and not inside(o2.export_bricks()[0], lo, hi).all()
-    # the other box: everything from the median brick y on goes
-    lo2, hi2 = np.asarray(c0, np.int64).min(0), np.asarray(c0, np.int64).max(0) + 1
-    hi2[1] = int(np.median(c0[:, 1]))
     n0 = g.num_bricks()
     n_ev = g.evict_outside(lo2, hi2, copy_out=False)
     assert 0 < n_ev < n0
-    twin = reference(o2, lambda c: inside(c, lo2, hi2), **kw)
     assert bitwise(g, twin)
     refs = Refs(g, (lo, hi), probes)
     print("evict, integrate, evict: %d of %d bricks removed, %s" % (n_ev, n0, counts(refs)))
@@ -326,9 +413,7 @@ def test_pipelined_unsynced(scans, probes):
     of its own; the references run on the oracle twin's export, which each volume's export must
     equal afterwards."""
     kw = kw_of()
-    o = ora(**kw)
-    for pts, org in scans:
-        o.integrate(pts, org)
+    o = build_twin(scans, **kw)
     refs = Refs(o, cut_box(o.export_bricks()[0]), probes)
     assert_not_vacuous(counts(refs))
     for kind in KINDS:

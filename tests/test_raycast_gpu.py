@@ -7,6 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import pastcap as pc
 import rayref as rr
 import sampleref as sr
 
@@ -275,6 +276,28 @@ def test_small_counts_device_pointers(maps, n):
         depth, normal, hit = raycast_device(m.vol, o, d, mode, normals=False, **kw)
         assert_same((depth[:n], None, hit[:n]), ref)
         assert np.all(normal == -7) and np.all(depth[n:] == -7) and np.all(hit[n:] == 9)
+
+
+def test_device_past_the_grid_cap(maps, scans):
+    """8192 * 256 + 77 rays: the last 77 are marched on a workgroup's second trip.  2039 distinct
+    rays repeated (tests/pastcap.py), so the reference marches 2039 rays; 2039 does not divide
+    the stride, so the ray one stride back is another one."""
+    m = maps["vdbfusion_f64"]
+    refs = pc.ray_references(m.field, scans[0])
+    idx, rot = pc.ray_tiling(refs)
+    sides = pc.ray_sides(refs, idx)
+    print("rotation %d: %s" % (rot, sides))
+    pc.assert_rays_past_cap(sides)
+    o, d = pc.ray_distinct(scans[0])
+    n = idx.size
+    assert n == pc.RAY_N and np.all(idx[pc.RAY_STRIDE:] != idx[:n - pc.RAY_STRIDE])
+    oo, dd = o[idx], d[idx]
+    kw = dict(zip(("t_min", "t_max", "step"), pc.RAY_T))
+    for mode in MODES:
+        ref = tuple(a[idx] for a in refs[mode])
+        depth, normal, hit = raycast_device(m.vol, oo, dd, mode, **kw)
+        assert_same((depth[:n], normal[:n], hit[:n]), ref)
+        assert np.all(depth[n:] == -7) and np.all(normal[n:] == -7) and np.all(hit[n:] == 9)
 
 
 def test_two_calls_give_the_same_bits(maps):
