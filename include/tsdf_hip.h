@@ -181,22 +181,34 @@ typedef struct tsdf_params {
  * pending; any other call (sync, query, export, import, stats, tsdf_integrate_batch_device)
  * flushes the queue first. */
 
+/* The counters (DESIGN.md §18 defines them and names the test that holds each to a reference;
+ * tests/test_stats_gpu.py).  A ray is a point that passes the range / far-ray / sector filters and
+ * walks (TSDF_VB_MERGED: a bundle); its samples are its gated voxels; a scan's U_vox is the distinct
+ * voxels among its samples (Voxblox: also a voxel whose fuse the nw < 1e-6 rule skips).  "since
+ * reset": since tsdf_create or the last tsdf_reset_stats.  Every total counts a batch once, when it
+ * commits: a batch that overflowed and is re-run after a capacity growth adds nothing for its
+ * failed run.  The *_last fields are the last batch that FINISHED, committed or not (after a
+ * successful tsdf_sync: the last committed one; a short last batch's numbers, not the largest
+ * batch's); tsdf_reset_stats does not clear them. */
 typedef struct tsdf_stats {
-    uint64_t n_scans;          /* scans integrated (queued scans are flushed first) */
-    uint64_t n_points_in;      /* points handed in */
-    uint64_t n_bricks;         /* allocated bricks */
-    uint64_t n_pairs_last;     /* (ray, brick) pairs of the last batch */
-    uint64_t n_active_last;    /* bricks touched by the last batch */
-    uint64_t n_voxels_last;    /* sum over the last batch's scans of their unique voxels */
-    uint64_t n_voxels_total;   /* sum over scans of U_vox (unique voxels of the scan) since reset */
-    uint64_t n_rays_total;     /* valid rays (after the range filter) since reset */
-    uint64_t n_dirty_total;    /* sum over batches of the distinct voxels the batch updated */
-    uint64_t n_batches;        /* GPU batches launched since reset */
+    uint64_t n_scans;          /* scans integrated since reset (queued scans are flushed first) */
+    uint64_t n_points_in;      /* points handed in since reset, before any filter (a sector context
+                                  under TSDF_SECTOR_RULE_INDEX: the points of its share) */
+    uint64_t n_bricks;         /* allocated bricks (never above max_bricks) */
+    uint64_t n_pairs_last;     /* (ray, brick) pairs of the last batch: sum over its rays of the
+                                  distinct bricks among the ray's samples */
+    uint64_t n_active_last;    /* distinct bricks sampled by the last batch */
+    uint64_t n_voxels_last;    /* sum over the last batch's scans of U_vox */
+    uint64_t n_voxels_total;   /* sum over scans of U_vox since reset */
+    uint64_t n_rays_total;     /* rays since reset (a ray without a sample counts too) */
+    uint64_t n_dirty_total;    /* sum over batches, since reset, of the batch's distinct sampled
+                                  voxels (over all its scans): <= the batch's sum of U_vox */
+    uint64_t n_batches;        /* GPU batches launched since reset (a re-run counts once) */
     double kernel_ms[8];       /* per-kernel-kind accumulated device time when profiling is on */
     uint64_t kernel_launches[8];
     /* ABI v4 */
-    uint64_t n_grows;          /* capacity growths since create */
-    uint64_t n_replayed;       /* batches re-run after a growth since create */
+    uint64_t n_grows;          /* capacity growths since create (tsdf_reset_stats keeps it) */
+    uint64_t n_replayed;       /* batches re-run after a growth since create (kept likewise) */
     uint64_t max_bricks;       /* current brick pool capacity */
     /* ABI v8 */
     uint64_t peer_mask;        /* contexts of tsdf_create_sharded: bit j set when context j's
@@ -343,7 +355,17 @@ int tsdf_set_profiling_period(tsdf_ctx* ctx, uint32_t every_mask, uint32_t perio
  * pairs, voxel updates (sum over its scans of U_vox), dirty voxels, active and new bricks, pool
  * size, overflow bits, whether it committed (a batch re-run after a capacity growth reports
  * committed: false first), SURVEY §8d's algorithmic bytes, and with profiling on the per-kernel
- * times, path time and GB/s.  With max_batch = 1 every line is one scan (SURVEY §5 metrics). */
+ * times, path time and GB/s.  With max_batch = 1 every line is one scan (SURVEY §5 metrics).
+ * The fields, as tsdf_stats defines the words: "batch" ids increase and are never
+ * reused (a re-run gets a new id); "scans", "points": the batch's scans and the points handed in
+ * with them; "rays", "pairs", "voxel_updates" (sum of U_vox): sums over its scans; "dirty_voxels":
+ * its distinct sampled voxels; "active_bricks": its distinct sampled bricks; "new_bricks": the
+ * active bricks this run of the batch put into the pool (a re-run leaves out those its failed run
+ * had already put there); "bricks": the pool once the batch's own bricks are in (a batch
+ * of empty scans: the pool as it found it), whatever a pipelined next batch has added since; "algorithmic_bytes" = 12 rays + 16 voxel_updates.  An
+ * uncommitted line holds what the failed run counted before it was given up.  The log is
+ * also drained before the device's ring of 256 records could wrap, so no line is dropped (a replay
+ * of more than 256 batches at once could drop the oldest of them). */
 int tsdf_set_metrics_log(tsdf_ctx* ctx, const char* path);
 
 /* Marching-cubes triangle mesh of the field (VDBFusion VDBVolume::extract_triangle_mesh; SURVEY

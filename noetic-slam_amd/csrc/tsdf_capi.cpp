@@ -565,6 +565,8 @@ static int launch(tsdf_ctx* c, const float* d_xyz, BatchDesc& D) {
         if (tm && c->plan.fused) tm->next(k_front, KIND_COMPACT, st);
         HIPCHK(c, launch_compact(B, T, W, c->G, par, c->plan.fused, st, kt(KIND_COMPACT)));
         c->ht.lap(HT_COMPACT);
+    } else {  // no compaction: the record's pool count is taken here instead
+        HIPCHK(c, launch_pool_mark(c->G, par, st));
     }
     if (cross && !lean) HIPCHK(c, hipEventRecord(c->ev_compact[par], st));  // after compact: 1
     // -- back end

@@ -258,7 +258,9 @@ struct Counters {
     uint32_t ovf;  // OVF_* raised by this batch's kernels
     uint32_t n_new;  // bricks the batch allocated (k_compact_scan)
     uint32_t n_act;  // sector sharding: k_count blocks with a ray of this GPU's sector (k_sector_flags)
-    uint32_t pad1[2];
+    uint32_t pool;   // pool_count once this batch's bricks are in (k_compact_scan): the record's
+                     // `bricks`; Globals::pool_count may already hold the next batch's (pipeline)
+    uint32_t pad1;
     unsigned long long n_vox[8];    // sum over scans of U_vox, sharded by blockIdx & 7
     unsigned long long n_rays[8];   // valid rays
     unsigned long long n_pairs[8];
@@ -355,6 +357,8 @@ hipError_t launch_place(const float* d_xyz, const BatchRef& D, const RayConst& R
                         const Work& Wk, Globals* G, int parity, hipStream_t st, const KTime& kt = {});
 hipError_t launch_finish(Globals* G, int parity, uint32_t batch_id, const BatchRef& D,
                          hipStream_t st);
+// A batch without a block runs no compaction: its Counters::pool is set in compaction's place
+hipError_t launch_pool_mark(Globals* G, int parity, hipStream_t st);
 // bytes (a multiple of 16) from device-accessible pinned host memory to device memory, then
 // *done = seq (done: device address of a pinned host word)
 hipError_t launch_upload(const void* host_src, void* dst, uint32_t bytes,

@@ -831,6 +831,7 @@ __global__ __launch_bounds__(CMP_SCAN_THREADS) void k_compact_scan(uint32_t nch,
         C->cursor = s_carry[1];
         C->n_new = s_carry[2] - G->pool_count;
         G->pool_count = s_carry[2];
+        C->pool = s_carry[2];
         if (fused ? s_carry[1] > Wk.max_spn : s_carry[1] > Wk.max_smp)
             atomicOr(&C->ovf, fused ? OVF_SPN : OVF_SMP);
         if (s_carry[0] > Wk.max_active) atomicOr(&C->ovf, OVF_ACTIVE);
@@ -1435,7 +1436,9 @@ __global__ void k_finish(Globals* G, int parity, uint32_t batch_id,
         r.n_new = C->n_new;
         r.ovf = ovf;
         r.committed = commit ? 1u : 0u;
-        r.pool_count = G->pool_count;
+        // the pool after THIS batch's compaction: under pipeline 1 / 2 the next batch's
+        // k_compact_scan may already have advanced G->pool_count
+        r.pool_count = C->pool;
         r.tiled = tiled;
         r.pad = 0u;
         r.rays = r.pairs = r.vox = r.dirty = 0ull;
@@ -1473,6 +1476,16 @@ hipError_t launch_upload(const void* host_src, void* dst, uint32_t bytes,
                          unsigned long long* done, unsigned long long seq, hipStream_t st) {
     k_upload<<<1, 256, 0, st>>>(static_cast<const uint4*>(host_src), static_cast<uint4*>(dst),
                                 bytes / 16, done, seq);
+    return hipGetLastError();
+}
+
+// A batch without a block (empty scans only) launches no k_compact_scan; in its place in the
+// stream, where the cross-batch waits keep the neighbouring batches' compactions away, this leaves
+// the pool count the batch's record reports.
+__global__ void k_pool_mark(Globals* G, int parity) { G->ctr[parity].pool = G->pool_count; }
+
+hipError_t launch_pool_mark(Globals* G, int parity, hipStream_t st) {
+    k_pool_mark<<<1, 1, 0, st>>>(G, parity);
     return hipGetLastError();
 }
 

@@ -6,6 +6,10 @@ reference for the domain clip that shares no code with the oracle or the kernels
 
 Scope: one scan into an empty map, origin-only (Voxblox point weight 1), no carving, no range
 limits; every ray's index coordinates far below 2^30 (the far-ray rule is not restated here).
+
+The three `_samples_*` walks return one (ijk, sdf, weight) part per DDA step; with rays=True every
+part carries a fourth array, the index of each sample's ray in the cloud (tests/statsref.py counts
+a ray's bricks from it).  The default return value is unchanged.
 """
 import numpy as np
 
@@ -15,8 +19,8 @@ FLT_MAX = F(3.402823466e+38)
 TWO32 = F(4294967296.0)
 
 
-def _samples_vdbfusion(p, org, vs, tau):
-    """walk_ray: fp32 throughout."""
+def _samples_vdbfusion(p, org, vs, tau, rays=False):
+    """walk_ray: fp32 throughout.  rays: every part also carries its samples' ray indices."""
     o = np.asarray(org, D).astype(F)
     inv = F(1.0) / vs
     d = p - o
@@ -39,7 +43,8 @@ def _samples_vdbfusion(p, org, vs, tau):
         proj = (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
         sdf = np.where(proj > 0, dist, -dist)
         keep = act & (proj != 0) & (sdf > -tau)
-        out.append((v[keep].copy(), np.minimum(sdf, tau)[keep], np.ones(keep.sum(), F)))
+        out.append((v[keep].copy(), np.minimum(sdf, tau)[keep], np.ones(keep.sum(), F))
+                   + ((np.nonzero(keep)[0],) if rays else ()))
         # math::MinIndex: ties resolve to the higher axis
         ax = np.where((tn[:, 0] < tn[:, 1]) & (tn[:, 0] < tn[:, 2]), 0,
                       np.where(tn[:, 1] < tn[:, 2], 1, 2))
@@ -50,7 +55,7 @@ def _samples_vdbfusion(p, org, vs, tau):
     return out
 
 
-def _samples_vdbfusion_f64(p, org, vs, tau):
+def _samples_vdbfusion_f64(p, org, vs, tau, rays=False):
     """walk_ray_vdb: double geometry, openvdb's float ray and DDA."""
     o = np.asarray(org, D)
     pd = p.astype(D)
@@ -83,7 +88,8 @@ def _samples_vdbfusion_f64(p, org, vs, tau):
         proj = a[:, 0] * b[:, 0] + (a[:, 1] * b[:, 1] + a[:, 2] * b[:, 2])
         sdf = ((proj / np.abs(proj)) * dist).astype(F)  # NaN where proj == 0: fails the gate
         keep = act & (sdf > -tau)
-        out.append((v[keep].copy(), np.where(tau < sdf, tau, sdf)[keep], np.ones(keep.sum(), F)))
+        out.append((v[keep].copy(), np.where(tau < sdf, tau, sdf)[keep], np.ones(keep.sum(), F))
+                   + ((np.nonzero(keep)[0],) if rays else ()))
         ax = np.where((tn[:, 0] < tn[:, 1]) & (tn[:, 0] < tn[:, 2]), 0,
                       np.where(tn[:, 1] < tn[:, 2], 1, 2))
         act = act & (tn[r, ax] <= t1i)
@@ -95,7 +101,7 @@ def _samples_vdbfusion_f64(p, org, vs, tau):
 VB_MIN_WEIGHT = F(1.0 / 65536.0)
 
 
-def _samples_voxblox(p, org, vs, tau):
+def _samples_voxblox(p, org, vs, tau, rays=False):
     """walk_ray_vb: fp32, Eigen's x + (y + z) reductions, point weight 1 with the dropoff."""
     o = np.asarray(org, D).astype(F)
     inv = F(1.0) / vs
@@ -122,7 +128,7 @@ def _samples_voxblox(p, org, vs, tau):
         sdf = depth - proj
         w = np.where(sdf < -vs, np.maximum((F(1.0) * (tau + sdf)) / (tau - vs), F(0)), F(1.0)).astype(F)
         keep = act & (w >= VB_MIN_WEIGHT)
-        out.append((v[keep].copy(), sdf[keep], w[keep]))
+        out.append((v[keep].copy(), sdf[keep], w[keep]) + ((np.nonzero(keep)[0],) if rays else ()))
         act = act & (k < steps)
         k += 1
         # Eigen minCoeff: the first minimum wins
