@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "../../include/tsdf_hip.h"
+#include "../../include/tsdf_hip_deskew.h"
 #include "../../include/tsdf_hip_esdf.h"
 #include "../../include/tsdf_hip_merge.h"
 #include "../../include/tsdf_hip_mesh.h"
@@ -41,6 +42,7 @@
 #include "host_pack.h"
 #include "merge_plan.h"
 #include "mesh_plan.h"
+#include "os_headers.h"
 #include "pack_pool.h"
 #include "prune_plan.h"
 #include "tsdf_device.h"
@@ -2315,57 +2317,7 @@ int tsdf_export_bricks(tsdf_ctx* c, int32_t* coords, float* sdf, float* weight, 
     return TSDF_OK;
 }
 
-// Ouster packet layouts per UDP profile (ouster_client/src/parsing.cpp:42-175): header / column /
-// footer sizes and, for RANGE, SIGNAL, REFLECTIVITY, NEAR_IR: (bytes, offset, mask, shift).
-static bool os_layout(const tsdf_os_format* f, OsLayout& L) {
-    if (!f || f->pixels_per_column == 0 || f->columns_per_packet == 0 || f->columns_per_frame == 0 ||
-        f->pixels_per_column > 4096)
-        return false;
-    L = OsLayout{};
-    L.h = f->pixels_per_column;
-    L.w = f->columns_per_frame;
-    L.cols_per_packet = f->columns_per_packet;
-    switch (f->profile) {
-        case TSDF_OS_LEGACY:
-            L.pixel_bytes = 12;
-            L.f[0] = {4, 0, 0x000FFFFFu, 0};
-            L.f[1] = {2, 6, 0, 0};
-            L.f[2] = {2, 4, 0, 0};
-            L.f[3] = {2, 8, 0, 0};
-            break;
-        case TSDF_OS_RNG19_RFL8_SIG16_NIR16:
-            L.pixel_bytes = 12;
-            L.f[0] = {4, 0, 0x0007FFFFu, 0};
-            L.f[1] = {2, 6, 0, 0};
-            L.f[2] = {1, 4, 0, 0};
-            L.f[3] = {2, 8, 0, 0};
-            break;
-        case TSDF_OS_RNG19_RFL8_SIG16_NIR16_DUAL:
-            L.pixel_bytes = 16;
-            L.f[0] = {4, 0, 0x0007FFFFu, 0};
-            L.f[1] = {2, 8, 0, 0};
-            L.f[2] = {1, 3, 0, 0};
-            L.f[3] = {2, 12, 0, 0};
-            break;
-        case TSDF_OS_RNG15_RFL8_NIR8:
-            L.pixel_bytes = 4;
-            L.f[0] = {2, 0, 0x7FFFu, -3};
-            L.f[1] = {0, 0, 0, 0};
-            L.f[2] = {1, 2, 0, 0};
-            L.f[3] = {1, 3, 0, -4};
-            break;
-        default:
-            return false;
-    }
-    L.legacy = f->profile == TSDF_OS_LEGACY ? 1u : 0u;
-    L.packet_header = L.legacy ? 0u : 32u;
-    L.col_header = L.legacy ? 16u : 12u;
-    const uint32_t col_footer = L.legacy ? 4u : 0u, packet_footer = L.legacy ? 0u : 32u;
-    L.col_bytes = L.col_header + L.h * L.pixel_bytes + col_footer;
-    L.packet_bytes = L.packet_header + L.cols_per_packet * L.col_bytes + packet_footer;
-    return true;
-}
-
+// Ouster packets: the layouts per UDP profile are os_layout (os_headers.h).
 int tsdf_os_packet_bytes(const tsdf_os_format* fmt, uint32_t* bytes) {
     OsLayout L;
     if (!bytes || !os_layout(fmt, L)) return TSDF_EINVAL;
@@ -2397,6 +2349,32 @@ int tsdf_os_cartesian_device(tsdf_ctx* c, const uint32_t* d_range, uint64_t n, c
     HIPCHK(c, hipSetDevice(c->device));
     const OsPose P = os_pose(pose);
     HIPCHK(c, launch_os_xyz(d_range, n, d_dir, d_off, P, d_xyz, c->stream));
+    return TSDF_OK;
+}
+
+// ---- motion-compensated frames (include/tsdf_hip_deskew.h) ---------------------------------------
+int tsdf_os_headers(const tsdf_os_format* fmt, const uint8_t* packets, uint32_t n_packets,
+                    uint64_t* timestamp, uint32_t* status, uint16_t* measurement_id) {
+    return os_headers(fmt, packets, n_packets, timestamp, status, measurement_id);
+}
+
+int tsdf_os_deskew_device(tsdf_ctx* c, const tsdf_os_format* fmt, const uint8_t* d_packets,
+                          uint32_t n_packets, const float* d_dir_cm, const float* d_off_cm,
+                          const float* d_col_pose, float* d_xyz, uint32_t* d_range_cm) {
+    if (!c) return TSDF_EINVAL;
+    OsLayout L;
+    if (!os_layout(fmt, L)) return fail(c, TSDF_EINVAL, "bad Ouster packet format");
+    if (!d_dir_cm || !d_off_cm || !d_col_pose || !d_xyz || (n_packets && !d_packets))
+        return fail(c, TSDF_EINVAL, "null argument");
+    if ((uint64_t)n_packets * L.cols_per_packet > (1ull << 20))
+        return fail(c, TSDF_EINVAL, "%llu packet columns exceed 2^20",
+                    (unsigned long long)n_packets * L.cols_per_packet);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t px = (size_t)L.h * L.w;
+    HIPCHK(c, hipMemsetAsync(d_xyz, 0xFF, px * 3 * sizeof(float), c->stream));
+    if (d_range_cm) HIPCHK(c, hipMemsetAsync(d_range_cm, 0, px * sizeof(uint32_t), c->stream));
+    HIPCHK(c, launch_os_deskew(d_packets, n_packets, L, d_dir_cm, d_off_cm, d_col_pose, d_xyz,
+                               d_range_cm, c->stream));
     return TSDF_OK;
 }
 

@@ -29,6 +29,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "os_headers.h"
+
 namespace tsdf {
 
 constexpr uint64_t EMPTY_KEY = ~0ull;
@@ -438,17 +440,7 @@ hipError_t launch_mg_prepass(const float* d_xyz, const BatchRef& B, uint32_t n_b
                              uint64_t n_points, const RayConst& R, MgBufs& M, uint32_t* ovf,
                              hipStream_t st);
 // Ouster packets (tsdf_ouster.hip)
-struct OsField {
-    uint32_t nbytes;  // little-endian source bytes (0: the profile has no such field)
-    uint32_t offset;  // byte offset in the pixel
-    uint32_t mask;    // 0: none
-    int32_t shift;    // > 0: right, < 0: left
-};
-struct OsLayout {
-    uint32_t h, w, cols_per_packet, packet_bytes, packet_header, col_header, col_bytes,
-        pixel_bytes, legacy;
-    OsField f[4];  // RANGE, SIGNAL, REFLECTIVITY, NEAR_IR
-};
+// OsField, OsLayout: os_headers.h (shared with the host's header parse)
 struct OsPose {
     float m[12];  // 3x4 row-major (rotation | translation), fp32
 };
@@ -456,6 +448,12 @@ hipError_t launch_os_decode(const uint8_t* d_packets, uint32_t n_packets, const 
                             uint32_t* const out[4], hipStream_t st);
 hipError_t launch_os_xyz(const uint32_t* d_range, uint64_t n, const float* d_dir,
                          const float* d_off, const OsPose& P, float* d_xyz, hipStream_t st);
+// packets -> world points under one pose per column (tsdf_deskew.hip; include/tsdf_hip_deskew.h):
+// d_dir / d_off / d_xyz / d_range column-major (index m_id * h + u); d_range may be null.  The
+// caller has filled d_xyz with 0xFF bytes and d_range with zeros.
+hipError_t launch_os_deskew(const uint8_t* d_packets, uint32_t n_packets, const OsLayout& L,
+                            const float* d_dir, const float* d_off, const float* d_col_pose,
+                            float* d_xyz, uint32_t* d_range, hipStream_t st);
 // marching cubes (tsdf_mesh.hip)
 // both case tables (TSDF_MC_GENERATED, TSDF_MC_LORENSEN); `tab` selects one per launch
 constexpr int MC_TABLES = 3;  // include/tsdf_hip.h TSDF_MC_TABLES

@@ -256,6 +256,16 @@ MESH_SIGNATURES = {
 }
 
 
+# include/tsdf_hip_deskew.h (TSDF_DESKEW_API): motion-compensated Ouster frames (the column headers
+# on the host, packets + one pose per column -> world points on the GPU), likewise a feature of
+# libtsdf_hip.so outside the contract, declared on the HIP library only.
+DESKEW_SIGNATURES = {
+    "tsdf_os_headers": (C.c_int, [C.POINTER(OsFormat), P, C.c_uint32, U64P, U32P,
+                                  C.POINTER(C.c_uint16)]),
+    "tsdf_os_deskew_device": (C.c_int, [P, C.POINTER(OsFormat), P, C.c_uint32, P, P, P, P, P]),
+}
+
+
 def declare(lib, names=None, optional=(), table=None):
     """Attach restype/argtypes for the ABI symbols present in `lib`; raise if a required one is
     missing.  table: the signature table (default SIGNATURES, the tsdf_hip.h contract)."""

@@ -44,6 +44,8 @@ def load_hip_library(path=None):
     _abi.declare(lib, table=_abi.MERGE_SIGNATURES)
     # ... and the indexed triangle mesh (include/tsdf_hip_mesh.h)
     _abi.declare(lib, table=_abi.MESH_SIGNATURES)
+    # ... and motion-compensated Ouster frames (include/tsdf_hip_deskew.h)
+    _abi.declare(lib, table=_abi.DESKEW_SIGNATURES)
     if lib.tsdf_abi_version() != ABI_VERSION:
         raise RuntimeError("libtsdf_hip.so ABI version mismatch")
     if path is None:

@@ -5,7 +5,10 @@ batched into a LidarScan (ouster_client/src/lidar_scan.cpp:540-633 ScanBatcher) 
 points with the xyz LUT (lidar_scan.cpp:297-382 make_xyz_lut, ouster/impl/cartesian.h).  Here the
 raw packets of a frame go to the GPU as bytes (the same 1.6 MB per 128 x 1024 frame as its xyz),
 are decoded there (tsdf_os_decode_device), turned into world points with the scan pose
-(tsdf_os_cartesian_device) and integrated, without a host-side point cloud.
+(tsdf_os_cartesian_device) and integrated, without a host-side point cloud.  On a moving platform
+every column takes the pose of its own timestamp instead (column_headers, column_poses,
+tsdf_os_deskew_device) and the frame is integrated as consecutive sub-scans (frame_segments,
+OusterFrontend.integrate_frame_deskewed; include/tsdf_hip_deskew.h).
 
 `read_pcap` / `split_frames` are the host side of a recorded stream (libpcap container, UDP
 payloads on the lidar port; frames grouped by frame_id, reordered packets of the previous frame
@@ -125,6 +128,77 @@ def destaggered_cloud(xyz, rng, signal, reflectivity, near_ir, pixel_shift_by_ro
     return out
 
 
+def column_headers(packets, fmt):
+    """(timestamp uint64[w], status uint32[w], measurement_id uint16[w]) of one frame's packets
+    (host bytes) under the SDK's ScanBatcher rule, through tsdf_os_headers (no GPU)."""
+    from ._lib import load_hip_library
+    buf = np.frombuffer(b"".join(packets), np.uint8)
+    ts = np.empty(fmt.w, np.uint64)
+    st = np.empty(fmt.w, np.uint32)
+    mid = np.empty(fmt.w, np.uint16)
+    rc = load_hip_library().tsdf_os_headers(
+        C.byref(fmt.c), C.c_void_p(buf.ctypes.data if buf.size else None), len(packets),
+        ts.ctypes.data_as(_abi.U64P), st.ctypes.data_as(_abi.U32P),
+        mid.ctypes.data_as(C.POINTER(C.c_uint16)))
+    if rc != _abi.TSDF_OK:
+        raise ValueError("bad Ouster format")
+    return ts, st, mid
+
+
+def _rotation_of(q):
+    """3x3 rotation of a quaternion (x, y, z, w), normalised first, float64."""
+    x, y, z, w = np.asarray(q, np.float64) / np.linalg.norm(q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def column_poses(track, timestamp, status, time_offset_ns=0, max_gap_ms=50.0):
+    """One pose per column from an ingest.PoseTrack that holds the SENSOR's pose in the world
+    frame: column v takes track.at(timestamp[v] + time_offset_ns).  Returns ((w, 3, 4) float64
+    matrices (rotation | translation), (w, 7) float64 (position, quaternion x y z w)); a row is all
+    NaN when the column is invalid (status bit 0 clear) or the track has no pose there (outside
+    the track, across a gap of more than max_gap_ms, a zero quaternion)."""
+    ts = np.asarray(timestamp, np.uint64)
+    st = np.asarray(status)
+    w = ts.shape[0]
+    mats = np.full((w, 3, 4), np.nan)
+    pose7 = np.full((w, 7), np.nan)
+    for v in range(w):
+        if not int(st[v]) & 1:
+            continue
+        pq = track.at(int(ts[v]) + int(time_offset_ns), max_gap_ms)
+        if pq is None or not np.all(np.isfinite(pq[0])) or not np.all(np.isfinite(pq[1])) \
+                or not np.any(pq[1]):
+            continue
+        pose7[v, :3], pose7[v, 3:] = pq
+        mats[v, :, :3] = _rotation_of(pq[1])
+        mats[v, :, 3] = pq[0]
+    return mats, pose7
+
+
+def frame_segments(col_pose7, h, segments):
+    """A frame of w columns (column-major points, h per column) cut into K = `segments`
+    consecutive sub-scans: (scan_offsets uint64[K + 1], poses float64[K, 7]).  b_k = floor(k w / K)
+    and scan_offsets[k] = h b_k (the index rule of TSDF_SECTOR_RULE_INDEX); segment k takes the
+    pose of its finite-pose column nearest (b_k + b_{k+1}) // 2, ties to the lower column; a
+    segment without one gets position 0 and the identity quaternion (its points are all NaN)."""
+    p7 = np.asarray(col_pose7, np.float64).reshape(-1, 7)
+    w, K = p7.shape[0], int(segments)
+    if not 1 <= K <= w:
+        raise ValueError("segments must be in [1, %d]" % w)
+    b = [(k * w) // K for k in range(K + 1)]
+    ok = np.all(np.isfinite(p7), axis=1)
+    poses = np.zeros((K, 7))
+    poses[:, 6] = 1.0
+    for k in range(K):
+        cols = np.arange(b[k], b[k + 1])[ok[b[k]:b[k + 1]]]
+        if cols.size:
+            mid = (b[k] + b[k + 1]) // 2
+            poses[k] = p7[cols[np.argmin(np.abs(cols - mid))]]  # argmin: the first (lower) on a tie
+    return np.asarray(b, np.uint64) * np.uint64(h), poses
+
+
 class OusterFrontend:
     """Packets of one frame -> device field images -> world points -> the volume, on the GPU.
     `volume` is a HipTSDFVolume; the work runs on its context's stream, so call sync() before
@@ -146,6 +220,12 @@ class OusterFrontend:
                             self.fmt.azimuth)
         self.lut_dir = torch.from_numpy(d.astype(np.float32)).to(self.device)
         self.lut_off = torch.from_numpy(o.astype(np.float32)).to(self.device)
+        # the same LUT column-major (index v * h + u), the packets' order: the deskew kernel's
+        def cm(a):
+            a = a.astype(np.float32).reshape(self.fmt.h, self.fmt.w, 3)
+            return np.ascontiguousarray(a.transpose(1, 0, 2)).reshape(-1, 3)
+        self.lut_dir_cm = torch.from_numpy(cm(d)).to(self.device)
+        self.lut_off_cm = torch.from_numpy(cm(o)).to(self.device)
         self._alive = []  # device buffers the library's stream may still read (until sync())
         torch.cuda.synchronize(self.device)  # the LUT upload ran on torch's stream
 
@@ -184,6 +264,50 @@ class OusterFrontend:
         xyz = self.points(imgs["RANGE"], pose)
         self.vol.integrate_device(xyz.data_ptr(), xyz.shape[0], np.asarray(pose, np.float64)[:3, 3])
         return imgs, xyz
+
+    def deskewed_points(self, packets, col_pose, with_range=False):
+        """World points (w*h, 3) float32 on the device, COLUMN-major (point v * h + u), each under
+        its own column's pose: col_pose (w, 3, 4) (or (w, 4, 4)) sensor -> world, uploaded as
+        float32 (tsdf_os_deskew_device).  A NaN triple where the column is missing or invalid, the
+        range is 0 or the pose row is NaN.  with_range: also the (w, h) decoded range image."""
+        import torch
+        m = np.asarray(col_pose, np.float64)
+        if m.ndim != 3 or m.shape[0] != self.fmt.w or m.shape[1] < 3 or m.shape[2] != 4:
+            raise ValueError("col_pose must be (%d, 3, 4)" % self.fmt.w)
+        m = np.ascontiguousarray(m[:, :3, :]).astype(np.float32).reshape(self.fmt.w, 12)
+        buf = torch.from_numpy(np.frombuffer(b"".join(packets), np.uint8).copy()).to(self.device)
+        pose = torch.from_numpy(m).to(self.device)
+        torch.cuda.current_stream(self.device).synchronize()  # uploads (torch's stream) done
+        n = self.fmt.w * self.fmt.h
+        xyz = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        rng = (torch.empty((self.fmt.w, self.fmt.h), dtype=torch.int32, device=self.device)
+               if with_range else None)
+        self.vol._check(self.vol._lib.tsdf_os_deskew_device(
+            self.vol._ctx, C.byref(self.fmt.c), C.c_void_p(buf.data_ptr() if len(packets) else None),
+            len(packets), C.c_void_p(self.lut_dir_cm.data_ptr()),
+            C.c_void_p(self.lut_off_cm.data_ptr()), C.c_void_p(pose.data_ptr()),
+            C.c_void_p(xyz.data_ptr()), C.c_void_p(rng.data_ptr() if with_range else None)),
+            "os_deskew")
+        self._alive += [buf, pose, xyz] + ([rng] if with_range else [])
+        return (xyz, rng) if with_range else xyz
+
+    def integrate_frame_deskewed(self, packets, track, segments=16, time_offset_ns=0,
+                                 max_gap_ms=50.0):
+        """Integrate one frame from a moving sensor: every column's points under the pose
+        `track` (an ingest.PoseTrack of the sensor in the world frame) has at the column's
+        timestamp, then the frame as `segments` consecutive sub-scans, each seen from the pose of
+        its middle column (frame_segments).  The headers are parsed from the host bytes, so
+        nothing is read back.  Returns (points, {"valid_columns", "columns_without_pose",
+        "segments"}); the points stay in use until sync()."""
+        ts, st, _ = column_headers(packets, self.fmt)
+        mats, pose7 = column_poses(track, ts, st, time_offset_ns, max_gap_ms)
+        xyz = self.deskewed_points(packets, mats)
+        offs, poses = frame_segments(pose7, self.fmt.h, segments)
+        self.vol.integrate_batch_device_pose(xyz.data_ptr(), offs, poses)
+        valid = (st & 1) != 0
+        return xyz, {"valid_columns": int(valid.sum()),
+                     "columns_without_pose": int((valid & np.isnan(pose7[:, 0])).sum()),
+                     "segments": int(poses.shape[0])}
 
     def sync(self):
         """Wait for the volume's queued work; the frontend's device buffers are released."""

@@ -847,6 +847,13 @@ class HipTSDFVolume(TSDFVolume):
         self._check(fn(self._ctx, C.c_void_p(int(d_xyz_ptr)), offs.ctypes.data_as(_abi.U64P),
                        org.shape[0], org.ctypes.data_as(_abi.D3)), "integrate_batch_device")
 
+    def integrate_batch_device_pose(self, d_xyz_ptr, scan_offsets, poses):
+        """integrate_batch_device with one (x, y, z, qx, qy, qz, qw) pose per scan, (n, 7)."""
+        p = np.asarray(poses, np.float64)
+        if p.ndim != 2 or p.shape[1] != 7:
+            raise ValueError("poses must be (n_scans, 7)")
+        self.integrate_batch_device(d_xyz_ptr, scan_offsets, p)
+
     def sample_device(self, d_xyz_ptr, n, d_sdf_ptr, d_weight_ptr, d_grad_ptr, d_valid_ptr,
                       mode="trilinear", min_weight=0.0):
         """`sample` for n device points (n x 3 float32) into caller-given device buffers: sdf and
