@@ -358,6 +358,7 @@ struct tsdf_ctx {
     std::vector<Logged> log;
     bool can_grow = false;  // G->retry: overflowed batches are skipped and replayed
     bool in_replay = false;
+    uint32_t ovf_refused = 0;  // OVF_* of batches re-run committing what fits, for tsdf_sync
     // metrics log (tsdf_set_metrics_log): one JSON line per finished batch
     FILE* metrics = nullptr;
     uint64_t metrics_next = 0;  // the next batch id to report
@@ -752,7 +753,7 @@ static_assert(offsetof(Globals, pool_count) == 0 && offsetof(Globals, overflow) 
               "the host reads and clears Globals' head by these offsets");
 // Zero `words` adjacent u32 fields from `first` on
 static hipError_t globals_clear(uint32_t* first, int words) {
-    const uint32_t z[2] = {0u, 0u};
+    const uint32_t z[3] = {0u, 0u, 0u};
     return hipMemcpy(first, z, 4 * words, hipMemcpyHostToDevice);
 }
 
@@ -829,10 +830,27 @@ static int drain_all(tsdf_ctx* c) {
     return TSDF_OK;
 }
 
+// Replay logged batches in order (their inputs are still valid); every batch complete on return.
+static int replay(tsdf_ctx* c, const tsdf_ctx::Logged* first, size_t n) {
+    int rc = TSDF_OK;
+    c->in_replay = true;
+    for (size_t j = 0; j < n && !rc; j++) {
+        tsdf_ctx::Logged L = first[j];
+        c->n_scans -= L.D.n_scans;
+        c->n_batches--;
+        c->n_replayed++;
+        rc = launch(c, L.xyz, L.D);
+    }
+    c->in_replay = false;
+    return rc ? rc : drain_all(c);
+}
+
 // With every batch complete: if a batch overflowed, grow the capacity it lacked and re-run the
 // batches from it (their inputs are still valid), until a round succeeds.  Without growth (hard
 // limit, or a non-growable overflow) the batches are re-run committing what fits, and tsdf_sync
-// reports the overflow.
+// reports the overflow.  A Merged batch with more distinct keys in a bucket than its LDS table
+// holds (OVF_MG) lacks no capacity of the context: that batch alone is re-run committing what fits
+// and reported by tsdf_sync; the context keeps growing for the batches after it.
 static int check_and_replay(tsdf_ctx* c) {
     for (int round = 0; round < 64; round++) {
         GlobalsCheck g;
@@ -846,10 +864,32 @@ static int check_and_replay(tsdf_ctx* c) {
             c->log.clear();
             return TSDF_OK;
         }
+        // the replay: from the first failed batch on, in order
+        size_t first = 0;
+        while (first < c->log.size() && (uint32_t)c->log[first].id != g.fail_id) first++;
+        if (first == c->log.size()) first = 0;
+        std::vector<tsdf_ctx::Logged> rep(c->log.begin() + first, c->log.end());
+        c->log.clear();
+        if (g.overflow == OVF_MG && !rep.empty()) {
+            // nothing to grow (every growable flag of an earlier round was cleared with its
+            // growth, so the first failed batch raised OVF_MG and nothing else): that batch with
+            // retry off, its flags kept on the host for tsdf_sync, then the others with retry on
+            HIPCHK(c, globals_clear(&c->G->overflow, 3));  // overflow, failed, retry
+            int rc = replay(c, rep.data(), 1);
+            if (rc) return rc;
+            uint32_t ovf = 0;
+            HIPCHK(c, hipMemcpy(&ovf, &c->G->overflow, sizeof ovf, hipMemcpyDeviceToHost));
+            c->ovf_refused |= ovf;
+            const uint32_t on[3] = {0u, 0u, 1u};  // overflow, failed, retry
+            HIPCHK(c, hipMemcpy(&c->G->overflow, on, sizeof on, hipMemcpyHostToDevice));
+            c->log.clear();
+            rc = replay(c, rep.data() + 1, rep.size() - 1);
+            if (rc) return rc;
+            continue;
+        }
         int rc = TSDF_ENOMEM;
-        // pair slots per ray are a geometric bound, and a merged bucket's distinct keys exceed its
-        // LDS table only for scans of more than ~2^22 points: not capacities to grow
-        if (!(g.overflow & (OVF_PAIRS | OVF_MG))) {
+        // pair slots per ray are a geometric bound: not a capacity to grow
+        if (!(g.overflow & OVF_PAIRS)) {
             rc = TSDF_OK;
             if (g.overflow & (OVF_TABLE | OVF_POOL | OVF_ACTIVE))
                 rc = grow_capacity(c, std::max<uint64_t>(g.pool_count, c->T.max_bricks + 1));
@@ -867,29 +907,13 @@ static int check_and_replay(tsdf_ctx* c) {
                                "span list", true);
             if (rc == TSDF_EHIP) return rc;
         }
-        // the replay: from the first failed batch on, in order
-        size_t first = 0;
-        while (first < c->log.size() && (uint32_t)c->log[first].id != g.fail_id) first++;
-        if (first == c->log.size()) first = 0;
-        std::vector<tsdf_ctx::Logged> rep(c->log.begin() + first, c->log.end());
-        c->log.clear();
         if (rc != TSDF_OK) {  // cannot grow: commit what fits from now on
             c->can_grow = false;
             HIPCHK(c, globals_clear(&c->G->failed, 2));  // failed, retry
         } else {  // grown: the replay re-raises whatever still does not fit
             HIPCHK(c, globals_clear(&c->G->overflow, 2));  // overflow, failed
         }
-        c->in_replay = true;
-        for (auto& L : rep) {
-            c->n_scans -= L.D.n_scans;
-            c->n_batches--;
-            c->n_replayed++;
-            rc = launch(c, L.xyz, L.D);
-            if (rc) break;
-        }
-        c->in_replay = false;
-        if (rc) return rc;
-        rc = drain_all(c);
+        rc = replay(c, rep.data(), rep.size());
         if (rc) return rc;
     }
     return fail(c, TSDF_ENOMEM, "capacity growth did not converge");
@@ -1902,18 +1926,24 @@ int tsdf_sync(tsdf_ctx* c) {
     if (rc) return rc;
     uint32_t ovf = 0;
     HIPCHK(c, hipMemcpy(&ovf, &c->G->overflow, sizeof ovf, hipMemcpyDeviceToHost));
+    const uint32_t dev = ovf;
+    ovf |= c->ovf_refused;  // batches check_and_replay re-ran committing what fits
+    c->ovf_refused = 0;
     if (ovf) {
-        HIPCHK(c, hipMemset(&c->G->overflow, 0, sizeof ovf));
+        if (dev) HIPCHK(c, hipMemset(&c->G->overflow, 0, sizeof ovf));
         if (ovf & ERR_MERGE_KEY)
             return fail(c, TSDF_EINVAL, "border merge: a tile's brick is not held by this context");
-        return fail(c, TSDF_ENOMEM, "capacity overflow (%s%s%s%s%s%s%s): updates were dropped",
+        return fail(c, TSDF_ENOMEM, "capacity overflow (%s%s%s%s%s%s%s%s): updates were dropped",
                     (ovf & OVF_TABLE) ? "hash table full; " : "",
                     (ovf & OVF_POOL) ? "brick pool exhausted; " : "",
                     (ovf & OVF_PAIRS) ? "ray brick-pair slots exceeded; " : "",
                     (ovf & OVF_ACTIVE) ? "active-brick list full; " : "",
                     (ovf & OVF_SMP) ? "sample list full; " : "",
                     (ovf & OVF_FB) ? "fallback pair list full; " : "",
-                    (ovf & OVF_SPN) ? "span list full; " : "");
+                    (ovf & OVF_SPN) ? "span list full; " : "",
+                    (ovf & OVF_MG) ? "merged integrator: more distinct voxels in one bucket of a "
+                                     "scan than its table holds, their points were not bundled; "
+                                   : "");
     }
     return TSDF_OK;
 }

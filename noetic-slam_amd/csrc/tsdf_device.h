@@ -102,8 +102,12 @@ constexpr uint32_t OVF_TABLE = 1u, OVF_POOL = 2u, OVF_PAIRS = 4u, OVF_ACTIVE = 8
                                    // the workgroup regions)
                    OVF_SPN = 64u,  // single walk: the batch's spans exceed the span list
                    OVF_MG = 128u;  // merged pre-pass: a bucket holds more distinct bundle keys
-                                   // than k_mg_group's LDS table (a scan of more than ~2^22
-                                   // points; not a growable capacity)
+                                   // than k_mg_group's LDS table (MG_TAB; a scan of more than
+                                   // ~2^22 points, or one whose voxels crowd one bucket).  Not
+                                   // a growable capacity: the host re-runs that batch alone
+                                   // committing what fits (the keys beyond the table keep their
+                                   // one-point rays), tsdf_sync reports it, and the context
+                                   // goes on growing for later batches
 // a border tile whose brick this context lacks (tsdf_border_merge_device; sticky like OVF_*)
 constexpr uint32_t ERR_MERGE_KEY = 1u << 8;
 

@@ -25,7 +25,10 @@
 // The walk kernels then run unchanged over the batch's slots (RayConst::ray_w), so block counts,
 // offsets and the ray layout stay those of the input; empty slots (NaN point, weight 0) leave at the
 // walk's init.  Limit: a bucket holds at most MG_TAB distinct keys (about 2 x its expected count;
-// scans of more than ~2^22 points may exceed it): beyond, the batch fails with OVF_MG.
+// scans of more than ~2^22 points may exceed it): beyond, the batch raises OVF_MG.  The keys that
+// found no slot keep their points' one-point rays; the host (check_and_replay) commits that batch
+// with what fits, tsdf_sync returns TSDF_ENOMEM naming the cause, and later batches are unaffected
+// (the context still grows its capacities for them).
 #include <hip/hip_runtime.h>
 
 #include "tsdf_device.h"
