@@ -29,6 +29,7 @@
 
 #include "../../include/tsdf_hip.h"
 #include "../../include/tsdf_hip_deskew.h"
+#include "../../include/tsdf_hip_columns.h"
 #include "../../include/tsdf_hip_esdf.h"
 #include "../../include/tsdf_hip_merge.h"
 #include "../../include/tsdf_hip_mesh.h"
@@ -38,6 +39,7 @@
 #include "../../include/tsdf_mc_tables.h"
 #include "brick_key.h"
 #include "ctx_plan.h"
+#include "columns_plan.h"
 #include "esdf_plan.h"
 #include "host_pack.h"
 #include "merge_plan.h"
@@ -2296,6 +2298,77 @@ int tsdf_esdf_dense(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], uint3
     if (rc) return rc;
     HIPCHK(c, hipMemcpy(dist, dd, B.total * 4, hipMemcpyDeviceToHost));
     if (flags) HIPCHK(c, hipMemcpy(flags, df, B.total, hipMemcpyDeviceToHost));
+    return TSDF_OK;
+}
+
+// ---- column maps of a box (include/tsdf_hip_columns.h) -------------------------------------------
+
+// The rules both entry points share (the output buffers apart), reported in the header's order; B:
+// the box and its brick columns.
+static int columns_args(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], float occ_band,
+                        float min_weight, uint32_t min_occ, uint32_t min_free, ColBox* B) {
+    if (!lo || !hi) return fail(c, TSDF_EINVAL, "columns: null argument");
+    const int a = columns_check(lo, hi, occ_band, min_weight, min_occ, min_free, B);
+    // (occ_band comes before min_weight; min_weight is map_query_args' own rule and text)
+    if (a == COL_ARG_BAND) return fail(c, TSDF_EINVAL, "columns: %s", columns_arg_text(a));
+    return map_query_args(c, "columns", "a column map of", TSDF_SAMPLE_NEAREST, min_weight,
+                          a == COL_ARG_WEIGHT ? nullptr : columns_arg_text(a));
+}
+
+int tsdf_column_map_device(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], float occ_band,
+                           float min_weight, uint32_t min_occ, uint32_t min_free, float* d_elev,
+                           float* d_ceil, uint16_t* d_n_occ, uint16_t* d_n_free, uint8_t* d_flags) {
+    if (!c) return TSDF_EINVAL;
+    ColBox B;
+    int rc = columns_args(c, lo, hi, occ_band, min_weight, min_occ, min_free, &B);
+    if (rc) return rc;
+    if (!B.cells) return TSDF_OK;
+    if (!d_elev && !d_ceil && !d_n_occ && !d_n_free && !d_flags)
+        return fail(c, TSDF_EINVAL, "columns: null buffer");
+    rc = drain(c);
+    if (rc) return rc;
+    HIPCHK(c, launch_column_map(c->T, c->Pl, lo, B, occ_band, min_weight, min_occ, min_free, c->R.bg,
+                                c->R.vs, d_elev, d_ceil, d_n_occ, d_n_free, d_flags, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return TSDF_OK;
+}
+
+int tsdf_column_map(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], float occ_band,
+                    float min_weight, uint32_t min_occ, uint32_t min_free, float* elev, float* ceil,
+                    uint16_t* n_occ, uint16_t* n_free, uint8_t* flags) {
+    if (!c) return TSDF_EINVAL;
+    ColBox B;
+    int rc = columns_args(c, lo, hi, occ_band, min_weight, min_occ, min_free, &B);
+    if (rc) return rc;
+    if (!B.cells) return TSDF_OK;
+    if (!elev && !ceil && !n_occ && !n_free && !flags)
+        return fail(c, TSDF_EINVAL, "columns: null buffer");
+    rc = drain(c);
+    if (rc) return rc;
+    // the device copy of the outputs asked for
+    Scratch out;
+    float *de = nullptr, *dc = nullptr;
+    uint16_t *dno = nullptr, *dnf = nullptr;
+    uint8_t* df = nullptr;
+    hipError_t e = hipSuccess;
+    if (e == hipSuccess && elev) e = out.get(c, &de, B.cells);
+    if (e == hipSuccess && ceil) e = out.get(c, &dc, B.cells);
+    if (e == hipSuccess && n_occ) e = out.get(c, &dno, B.cells);
+    if (e == hipSuccess && n_free) e = out.get(c, &dnf, B.cells);
+    if (e == hipSuccess && flags) e = out.get(c, &df, B.cells);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, TSDF_ENOMEM, "columns: output allocation for %llu columns failed",
+                    (unsigned long long)B.cells);
+    }
+    HIPCHK(c, launch_column_map(c->T, c->Pl, lo, B, occ_band, min_weight, min_occ, min_free, c->R.bg,
+                                c->R.vs, de, dc, dno, dnf, df, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (elev) HIPCHK(c, hipMemcpy(elev, de, B.cells * 4, hipMemcpyDeviceToHost));
+    if (ceil) HIPCHK(c, hipMemcpy(ceil, dc, B.cells * 4, hipMemcpyDeviceToHost));
+    if (n_occ) HIPCHK(c, hipMemcpy(n_occ, dno, B.cells * 2, hipMemcpyDeviceToHost));
+    if (n_free) HIPCHK(c, hipMemcpy(n_free, dnf, B.cells * 2, hipMemcpyDeviceToHost));
+    if (flags) HIPCHK(c, hipMemcpy(flags, df, B.cells, hipMemcpyDeviceToHost));
     return TSDF_OK;
 }
 

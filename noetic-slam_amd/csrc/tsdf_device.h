@@ -515,6 +515,13 @@ hipError_t launch_esdf(const Table& T, const Pool& Pl, const int64_t lo[3], cons
                        uint32_t radius, float band, float min_w, float bg, float vs, uint16_t* d_g0,
                        uint16_t* d_g1, uint8_t* d_cls, float* d_dist, uint8_t* d_flags,
                        hipStream_t st);
+// column maps of a box (tsdf_columns.hip; include/tsdf_hip_columns.h): B is columns_check's box of
+// voxels lo..lo + n - 1 (columns_plan.h); nx ny cells per output, any of the five may be null
+struct ColBox;
+hipError_t launch_column_map(const Table& T, const Pool& Pl, const int64_t lo[3], const ColBox& B,
+                             float band, float min_w, uint32_t min_occ, uint32_t min_free, float bg,
+                             float vs, float* d_elev, float* d_ceil, uint16_t* d_n_occ,
+                             uint16_t* d_n_free, uint8_t* d_flags, hipStream_t st);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, uint64_t n, hipStream_t st);
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, uint64_t n, hipStream_t st);
 // removing bricks (tsdf_prune.hip; include/tsdf_hip_prune.h), over the pool slots [0, n)

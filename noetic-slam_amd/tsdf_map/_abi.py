@@ -216,6 +216,22 @@ ESDF_SIGNATURES = {
     "tsdf_esdf_dense_device": (C.c_int, [P, L3, L3, C.c_uint32, C.c_float, C.c_float, P, P]),
 }
 
+# include/tsdf_hip_columns.h (TSDF_COLUMNS_API): the column maps of a map box (elevation, ceiling,
+# occupancy per x, y cell), likewise a feature of libtsdf_hip.so outside the contract, declared on
+# the HIP library only.
+COLUMN_OBSERVED = 1   # TSDF_COLUMN_OBSERVED: n_occ + n_free > 0
+COLUMN_OCCUPIED = 2   # TSDF_COLUMN_OCCUPIED: n_occ >= min_occ
+COLUMN_FREE = 4       # TSDF_COLUMN_FREE: not OCCUPIED and n_free >= min_free
+COLUMN_HAS_ELEV = 8   # TSDF_COLUMN_HAS_ELEV: the column has an up crossing
+COLUMN_HAS_CEIL = 16  # TSDF_COLUMN_HAS_CEIL: the column has a down crossing
+U16P = C.POINTER(C.c_uint16)
+COLUMNS_SIGNATURES = {
+    "tsdf_column_map": (C.c_int, [P, L3, L3, C.c_float, C.c_float, C.c_uint32, C.c_uint32, FP, FP,
+                                  U16P, U16P, U8P]),
+    "tsdf_column_map_device": (C.c_int, [P, L3, L3, C.c_float, C.c_float, C.c_uint32, C.c_uint32,
+                                         P, P, P, P, P]),
+}
+
 # include/tsdf_hip_merge.h (TSDF_MERGE_API): one map merged into another under a rigid transform,
 # likewise a feature of libtsdf_hip.so outside the contract, declared on the HIP library only.
 # Modes: SAMPLE_MODES.

@@ -40,6 +40,8 @@ def load_hip_library(path=None):
     _abi.declare(lib, table=_abi.PRUNE_SIGNATURES)
     # ... and the distance field of a box (include/tsdf_hip_esdf.h)
     _abi.declare(lib, table=_abi.ESDF_SIGNATURES)
+    # ... and the column maps of a box (include/tsdf_hip_columns.h)
+    _abi.declare(lib, table=_abi.COLUMNS_SIGNATURES)
     # ... and merging a map into another under a rigid transform (include/tsdf_hip_merge.h)
     _abi.declare(lib, table=_abi.MERGE_SIGNATURES)
     # ... and the indexed triangle mesh (include/tsdf_hip_mesh.h)

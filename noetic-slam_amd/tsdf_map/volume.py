@@ -380,6 +380,47 @@ class TSDFVolume:
                        flags.ctypes.data_as(_abi.U8P)), "esdf")
         return dist, flags
 
+    # -- column maps of a box (include/tsdf_hip_columns.h) ----------------------------------------
+    def _columns_fn(self, name):
+        """An entry point of include/tsdf_hip_columns.h, detected by the symbol like `_sample_fn`."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (the column maps are part of "
+                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    @staticmethod
+    def _columns_args(lo, hi, min_occ, min_free):
+        lo = np.ascontiguousarray(np.asarray(lo, np.int64).reshape(3))
+        hi = np.ascontiguousarray(np.asarray(hi, np.int64).reshape(3))
+        if np.any(hi < lo):
+            raise ValueError("hi < lo")
+        for name, v in (("min_occ", min_occ), ("min_free", min_free)):
+            if not 1 <= int(v) <= 65535:
+                raise ValueError("%s must be in 1..65535" % name)
+        return lo, hi, int(min_occ), int(min_free)
+
+    def column_map(self, lo, hi, occ_band=0.0, min_weight=0.0, min_occ=1, min_free=1):
+        """The column maps of voxels lo..hi-1 as a `gridmap.ColumnMap` of [y, x] arrays: elev (the
+        height in metres of the highest surface facing +z, NaN where the column has none), ceil
+        (the lowest surface facing -z), n_occ / n_free (the observed voxels with sdf <= occ_band /
+        above it), flags (COLUMN_* of tsdf_map._abi).  A voxel is observed when W > 0 and
+        W >= min_weight; a column is OCCUPIED with n_occ >= min_occ, else FREE with
+        n_free >= min_free, else unknown.  include/tsdf_hip_columns.h states the rules."""
+        from .gridmap import ColumnMap
+        lo, hi, min_occ, min_free = self._columns_args(lo, hi, min_occ, min_free)
+        fn = self._columns_fn("tsdf_column_map")
+        shape = (int(hi[1] - lo[1]), int(hi[0] - lo[0]))
+        elev, ceil = np.empty(shape, np.float32), np.empty(shape, np.float32)
+        n_occ, n_free = np.empty(shape, np.uint16), np.empty(shape, np.uint16)
+        flags = np.empty(shape, np.uint8)
+        self._check(fn(self._ctx, lo.ctypes.data_as(_abi.L3), hi.ctypes.data_as(_abi.L3),
+                       float(occ_band), float(min_weight), min_occ, min_free,
+                       elev.ctypes.data_as(_abi.FP), ceil.ctypes.data_as(_abi.FP),
+                       n_occ.ctypes.data_as(_abi.U16P), n_free.ctypes.data_as(_abi.U16P),
+                       flags.ctypes.data_as(_abi.U8P)), "column_map")
+        return ColumnMap(elev, ceil, n_occ, n_free, flags, lo, hi, self.voxel_size)
+
     def extract_triangle_mesh(self, fill_holes=True, min_weight=0.0, table="generated",
                               halo=None):
         """VDBVolume.extract_triangle_mesh: (vertices (3T, 3) float32, triangles (T, 3) int64) —
@@ -896,6 +937,21 @@ class HipTSDFVolume(TSDFVolume):
                        band, float(min_weight), C.c_void_p(dist.data_ptr()),
                        C.c_void_p(fl.data_ptr() if flags else 0)), "esdf_device")
         return dist, fl
+
+    def column_map_device(self, lo, hi, occ_band=0.0, min_weight=0.0, min_occ=1, min_free=1):
+        """`column_map` into device tensors on the volume's GPU: (elev, ceil float32, n_occ, n_free
+        uint16, flags uint8), each [y, x], complete when the call returns."""
+        import torch
+        lo, hi, min_occ, min_free = self._columns_args(lo, hi, min_occ, min_free)
+        fn = self._columns_fn("tsdf_column_map_device")
+        shape = (int(hi[1] - lo[1]), int(hi[0] - lo[0]))
+        out = [torch.empty(shape, dtype=dt, device=self.tensor_device)
+               for dt in (torch.float32, torch.float32, torch.uint16, torch.uint16, torch.uint8)]
+        torch.cuda.synchronize(out[0].device)
+        self._check(fn(self._ctx, lo.ctypes.data_as(_abi.L3), hi.ctypes.data_as(_abi.L3),
+                       float(occ_band), float(min_weight), min_occ, min_free,
+                       *[C.c_void_p(t.data_ptr()) for t in out]), "column_map_device")
+        return tuple(out)
 
     def indexed_mesh_device(self, min_weight=0.0, table="generated", lo=None, hi=None,
                             normals=True):
