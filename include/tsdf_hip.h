@@ -154,7 +154,12 @@ typedef struct tsdf_params {
      * TSDF_SECTOR_RULE_WORLD: the world-frame pseudo-angle sectors of tsdf_sector_of (ABI v4-v9's
      * only rule): a brick's owner stays fixed while the sensor turns, at the price of every
      * context reading every point (the kernels drop the other sectors' rays).
-     * Either rule partitions each cloud's rays, so the reduced field is the unsharded one. */
+     * Either rule partitions each cloud's points.  Under the VDBFusion semantics the reduced field
+     * is then the unsharded one up to fp32 rounding (same voxels, weights exact).  Under Voxblox
+     * the reduce is approximate (the clamped update is order-dependent), and under the index rule
+     * a TSDF_VB_MERGED context bundles its own share only, so a voxel whose points lie on both
+     * sides of a share boundary casts two rays and the weights differ from the one-context map
+     * (DESIGN.md §22 has the measured differences). */
     int32_t sector_rule;
 } tsdf_params;
 
@@ -473,8 +478,9 @@ int tsdf_brick_keys_device(tsdf_ctx* ctx, uint64_t* d_keys, uint64_t cap, uint64
 
 /* d_all_keys: world blocks of `stride` keys (device), block r = rank r's keys, counts[r] valid
  * (host array).  Packs the bricks of this context owned by a lower rank into d_send (device, rows
- * of TSDF_TILE_WORDS, grouped by owner rank ascending; cap_rows rows) and resets them.
- * send_counts[world] (host) receives the rows per destination; d_send == NULL only counts. */
+ * of TSDF_TILE_WORDS, grouped by owner rank ascending; cap_rows rows); they keep their mass until
+ * tsdf_border_commit_device.  send_counts[world] (host) receives the rows per destination;
+ * d_send == NULL only counts. */
 int tsdf_border_pack_device(tsdf_ctx* ctx, const uint64_t* d_all_keys, const uint64_t* counts,
                             uint64_t stride, uint32_t world, uint32_t rank, uint32_t* d_send,
                             uint64_t cap_rows, uint64_t* send_counts);
