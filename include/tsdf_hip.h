@@ -124,7 +124,14 @@ typedef struct tsdf_params {
      * per-sample weight is capped at min(max_weight, TSDF_W0_CAP) (without a cap a point near the
      * sensor plane, |z| ~ 1e-5, overflows the exact fixed-point sums), and scans given as a bare
      * origin (tsdf_integrate, tsdf_integrate_device, tsdf_integrate_batch_device) carry no
-     * orientation and take w = 1.  0: w = 1 (use_const_weight = true). */
+     * orientation and take w = 1.  0: w = 1 (use_const_weight = true).
+     * The cap bounds one sample, not a sum: a voxel's sums over ONE scan are signed 64-bit with
+     * 32 fraction bits (sum of trunc(w 2^32), sum of trunc(s w 2^32), |s| up to sdf_trunc plus a
+     * voxel's half diagonal), so n samples of weight w in one voxel of one scan are exact only
+     * while n w < 2^31 and n |s| w < 2^31.  With max_weight < 2^16 / max(1, |s|) that holds for
+     * every scan of up to 2^15 points; with max_weight >= 2^16 it holds for 2^15 / max(1, |s|)
+     * capped samples per voxel and scan (tests/test_band_sweep_gpu.py stays inside it), and a
+     * max_points-sized scan of such points into one voxel is outside it. */
     int32_t depth_weight;
     /* ABI v8: Voxblox's integrator (TSDF_SEM_VOXBLOX only; voxblox_ros TsdfServer `method`).
      * TSDF_VB_SIMPLE (default): every point casts its own ray (SimpleTsdfIntegrator).

@@ -328,9 +328,10 @@ __device__ __forceinline__ bool vb_init(const RayConst& R, const BatchRef& D, ui
     r.rem = min(steps, MAX_DDA_STEPS - 1);
     // TsdfIntegratorBase::getVoxelWeight: 1 / z^2 of the point's sensor-frame depth z (the scan's
     // z axis dotted with p - o, Eigen's x + (y + z)); |z| <= kEpsilon (1e-6) gives 0.  The weight
-    // is capped at R.w0_cap = min(max_weight, 2^16) so the int64 fixed-point sums cannot overflow
-    // (upstream's per-update max_weight cap bounds the fused weight the same way).  A scan without
-    // an orientation (origin-only entry points: zero axis) takes the constant weight 1.
+    // is capped at R.w0_cap = min(max_weight, 2^16) so that the int64 fixed-point sums hold
+    // 2^15 / max(1, |s|) capped samples per voxel and scan (include/tsdf_hip.h depth_weight has
+    // the bound; upstream's per-update max_weight cap bounds the fused weight the same way).  A
+    // scan without an orientation (origin-only entry points: zero axis) takes the constant weight 1.
     r.w0 = 1.0f;
     if (R.ray_w) {
         r.w0 = fabsf(bw);

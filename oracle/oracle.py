@@ -53,6 +53,9 @@ def load():
         lib.tsdf_oracle_ray_voxels.restype = C.c_int64
         lib.tsdf_oracle_ray_voxels.argtypes = [C.c_void_p, _abi.FP, _abi.D3, _abi.I3, _abi.FP,
                                                C.c_uint64]
+        lib.tsdf_oracle_ray_facts.restype = C.c_int64
+        lib.tsdf_oracle_ray_facts.argtypes = [C.c_void_p, _abi.FP, C.c_uint64, _abi.D3, C.c_int32,
+                                              _abi.I3, _abi.I3, _abi.I3, C.c_uint64]
         _lib = lib
     return _lib
 
@@ -92,3 +95,22 @@ class OracleTSDFVolume(TSDFVolume):
         if k < 0:
             return None
         return ijk[:min(k, cap)], s[:min(k, cap)]
+
+    def ray_facts(self, points, extrinsic):
+        """Every ray of one scan walked as integrate(points, extrinsic) would walk it (the context's
+        own semantics and precisions, a (7,) pose's z axis, method="merged": the scan's bundles),
+        the map untouched: (visited, gated, runs) int32 arrays, one row per point (merged: per
+        bundle).  visited: the DDA's voxels, -1 for a ray the filters drop; gated: the voxels
+        handed to the fuse; runs: the runs of consecutive gated voxels in one brick."""
+        p = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        e = np.ascontiguousarray(np.asarray(extrinsic, np.float64).reshape(-1))
+        if e.shape[0] not in (3, 7):
+            raise ValueError("extrinsic must be a (3,) origin or a (7,) pose")
+        n = p.shape[0]
+        out = [np.zeros(max(n, 1), np.int32) for _ in range(3)]
+        k = self._lib.tsdf_oracle_ray_facts(self._ctx, p.ctypes.data_as(_abi.FP), n,
+                                            e.ctypes.data_as(_abi.D3), 1 if e.shape[0] == 7 else 0,
+                                            *[a.ctypes.data_as(_abi.I3) for a in out], n)
+        if k < 0:
+            raise MemoryError("tsdf_oracle_ray_facts failed")
+        return tuple(a[:k] for a in out)

@@ -1453,6 +1453,80 @@ int64_t tsdf_oracle_ray_voxels(tsdf_ctx* c, const float p[3], const double origi
     return (int64_t)r.n;
 }
 
+/* Per-ray facts of one scan, walked as tsdf_integrate / tsdf_integrate_pose would walk it (the
+ * walk of the context's semantics -- TSDF_SEM_VDBFUSION_F64 at upstream's precisions, which
+ * tsdf_oracle_ray_voxels does not take --, the pose's z axis for 1/z^2 weights, the bundles of
+ * TSDF_VB_MERGED) without touching the map.  Row r is the scan's r-th point (merged: bundle):
+ * visited[r] the DDA's voxels, gated or not (-1: the ray is dropped), gated[r] the voxels handed to
+ * the fuse, runs[r] the runs of consecutive gated voxels in one brick (k_count's pairs).  Returns
+ * the rows written (the points; merged: the bundles), -1 on a failed allocation or a short cap. */
+typedef struct {
+    int32_t n, runs, b[3];
+} facts_rec;
+
+static void visit_facts(tsdf_ctx* c, int32_t x, int32_t y, int32_t z, float s, float w,
+                        void* user) {
+    (void)c;
+    (void)s;
+    (void)w;
+    facts_rec* r = (facts_rec*)user;
+    const int32_t bx = x >> 3, by = y >> 3, bz = z >> 3;
+    if (r->n == 0 || bx != r->b[0] || by != r->b[1] || bz != r->b[2]) r->runs++;
+    r->b[0] = bx; r->b[1] = by; r->b[2] = bz;
+    r->n++;
+}
+
+int64_t tsdf_oracle_ray_facts(tsdf_ctx* c, const float* xyz, uint64_t n, const double* ext,
+                              int32_t has_pose, int32_t* visited, int32_t* gated, int32_t* runs,
+                              uint64_t cap) {
+    if (!c || (!xyz && n) || !ext || !visited || !gated || !runs) return -1;
+    c->zax[0] = 0.0f; c->zax[1] = 0.0f; c->zax[2] = 0.0f;
+    if (has_pose) { /* tsdf_integrate_pose's axis */
+        const double nn = sqrt(ext[3] * ext[3] + ext[4] * ext[4] + ext[5] * ext[5] + ext[6] * ext[6]);
+        if (!(nn > 0.0) || !isfinite(nn)) return -1;
+        const double x = ext[3] / nn, y = ext[4] / nn, z = ext[5] / nn, w = ext[6] / nn;
+        c->zax[0] = (float)(2.0 * (x * z + w * y));
+        c->zax[1] = (float)(2.0 * (y * z - w * x));
+        c->zax[2] = (float)(1.0 - 2.0 * (x * x + y * y));
+    }
+    const float ox = (float)ext[0], oy = (float)ext[1], oz = (float)ext[2];
+    const int merged = c->sem == TSDF_SEM_VOXBLOX && c->p.voxblox_method == TSDF_VB_MERGED;
+    const float* rows = xyz;
+    uint32_t step = 3;
+    float* b = NULL;
+    if (merged) {
+        uint64_t nb = 0;
+        b = mg_bundle(c, (const char*)xyz, n, 12, 0, 0, ox, oy, oz, &nb);
+        if (!b) return -1;
+        rows = b;
+        step = 4;
+        n = nb;
+    }
+    if (n > cap) {
+        free(b);
+        return -1;
+    }
+    const int vdb_walk = c->sem == TSDF_SEM_VDBFUSION_F64 || c->mode == ORACLE_MODE_VDB_LITERAL;
+    for (uint64_t i = 0; i < n; i++) {
+        const float* q = rows + i * step;
+        facts_rec r = {0, 0, {0, 0, 0}};
+        int64_t v;
+        if (vdb_walk) {
+            const double pd[3] = {q[0], q[1], q[2]};
+            v = walk_ray_vdb(c, pd, ext, visit_facts, &r);
+        } else if (c->sem == TSDF_SEM_VOXBLOX) {
+            v = walk_ray_vb(c, q[0], q[1], q[2], ox, oy, oz, merged ? q[3] : 0.0f, visit_facts, &r);
+        } else {
+            v = walk_ray(c, q[0], q[1], q[2], ox, oy, oz, visit_facts, &r);
+        }
+        visited[i] = v < 0 ? -1 : (int32_t)(v > 0x7fffffff ? 0x7fffffff : v);
+        gated[i] = v < 0 ? 0 : r.n;
+        runs[i] = v < 0 ? 0 : r.runs;
+    }
+    free(b);
+    return (int64_t)n;
+}
+
 /* Host-side azimuth sector selection (same contract as the GPU library's). */
 int32_t tsdf_sector_of(float px, float py, const double origin[3], double yaw0,
                        uint32_t n_sectors) {
