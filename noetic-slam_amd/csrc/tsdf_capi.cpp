@@ -29,6 +29,7 @@
 
 #include "../../include/tsdf_hip.h"
 #include "../../include/tsdf_hip_deskew.h"
+#include "../../include/tsdf_hip_coarsen.h"
 #include "../../include/tsdf_hip_columns.h"
 #include "../../include/tsdf_hip_esdf.h"
 #include "../../include/tsdf_hip_merge.h"
@@ -38,6 +39,7 @@
 #include "../../include/tsdf_hip_sample.h"
 #include "../../include/tsdf_mc_tables.h"
 #include "brick_key.h"
+#include "coarsen_plan.h"
 #include "ctx_plan.h"
 #include "columns_plan.h"
 #include "esdf_plan.h"
@@ -2864,6 +2866,142 @@ int tsdf_merge_count(tsdf_ctx* dst, tsdf_ctx* src, const double pose[12], int32_
 int tsdf_merge_transformed(tsdf_ctx* dst, tsdf_ctx* src, const double pose[12], int32_t mode,
                            float min_weight, tsdf_merge_stats* out) {
     return merge_impl(dst, src, pose, mode, min_weight, out, true);
+}
+
+}  // extern "C"
+
+// ---- coarsening a map 2:1 into a map of twice the voxel size (include/tsdf_hip_coarsen.h; kernels
+// in tsdf_coarsen.hip; the rules, the index arithmetic and the scratch sizes: coarsen_plan.h;
+// DESIGN.md §24)
+
+// One context's part of the entry rules (merge_ctx_state's)
+static int coarsen_ctx_state(tsdf_ctx* d, tsdf_ctx* c, const char* which) {
+    if (c->p.n_sectors > 1)
+        return fail(d, TSDF_EINVAL, "coarsen: the %s context holds one sector shard of the map "
+                                    "(n_sectors > 1); coarsening a sharded field is not supported",
+                    which);
+    if (c->brd_open)
+        return fail(d, TSDF_EINVAL, "coarsen: a border reduce is open on the %s context: commit or "
+                                    "abort it first (tsdf_border_commit_device)", which);
+    return TSDF_OK;
+}
+
+static int coarsen_impl(tsdf_ctx* d, tsdf_ctx* s, const int32_t* lo, const int32_t* hi, int32_t side,
+                        uint32_t min_children, float min_weight, tsdf_coarsen_stats* out,
+                        bool apply) {
+    if (!d) return TSDF_EINVAL;
+    if (!s) return fail(d, TSDF_EINVAL, "coarsen: the source context is NULL");
+    if (s == d) return fail(d, TSDF_EINVAL, "coarsen: source and destination are the same context");
+    if (!apply && !out) return fail(d, TSDF_EINVAL, "coarsen: null argument");
+    int rule = coarsen_args(side, lo != nullptr, hi != nullptr, min_children, min_weight);
+    if (rule) return fail(d, TSDF_EINVAL, "coarsen: %s", coarsen_arg_text(rule));
+    if (s->device != d->device)
+        return fail(d, TSDF_EINVAL, "coarsen: the contexts are on different devices (%d and %d)",
+                    d->device, s->device);
+    rule = coarsen_compat(d->p.voxel_size, s->p.voxel_size, d->p.sdf_trunc, s->p.sdf_trunc,
+                          d->p.semantics, s->p.semantics);
+    if (rule) return fail(d, TSDF_EINVAL, "coarsen: %s", coarsen_compat_text(rule));
+    int rc = coarsen_ctx_state(d, d, "destination");
+    if (!rc) rc = coarsen_ctx_state(d, s, "source");
+    if (rc) return rc;
+    HIPCHK(d, hipSetDevice(d->device));  // (both contexts': the scratch and every launch below)
+    uint64_t n_src = 0, n_dst = 0;
+    rc = pool_bricks(s, &n_src);
+    if (rc) return fail(d, rc, "coarsen: the source context failed: %s", s->err.c_str());
+    rc = pool_bricks(d, &n_dst);
+    if (rc) return rc;
+    tsdf_coarsen_stats st{};
+    if (out) *out = st;
+    if (!n_src) return TSDF_OK;
+
+    CoarsenSel sel{};
+    if (lo) {
+        sel.has_box = 1;
+        sel.side = side;
+        for (int a = 0; a < 3; a++) {
+            sel.lo[a] = lo[a];
+            sel.hi[a] = hi[a];
+        }
+    }
+    Scratch tmp;
+    unsigned long long* ctr = nullptr;
+    std::vector<unsigned long long> hc(COARSEN_CTR_WORDS, 0);
+    const uint64_t slots = coarsen_set_slots(n_src);
+    uint64_t *set = nullptr, *list = nullptr;
+    uint32_t *flag = nullptr, *tslot = nullptr;
+    if (tmp.get(d, &ctr, COARSEN_CTR_WORDS) != hipSuccess || tmp.get(d, &set, slots) != hipSuccess ||
+        tmp.get(d, &list, n_src) != hipSuccess || tmp.get(d, &flag, n_src) != hipSuccess ||
+        tmp.get(d, &tslot, n_src) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(d, TSDF_ENOMEM, "coarsen: no device memory for %llu bytes of scratch",
+                    (unsigned long long)coarsen_scratch_bytes(n_src));
+    }
+    HIPCHK(d, hipMemsetAsync(ctr, 0, COARSEN_CTR_WORDS * 8, d->stream));
+    HIPCHK(d, launch_fill_u64(set, EMPTY_KEY, slots, d->stream));
+    HIPCHK(d, launch_coarsen_parents(s->T.brick_keys, (uint32_t)n_src, sel, set, slots, list, ctr,
+                                     d->stream));
+    // the selection's two counts: an empty selection launches nothing more, and the per-brick
+    // kernels get the list's exact length
+    HIPCHK(d, hipMemcpyAsync(hc.data(), ctr, 16, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
+    const uint64_t n_sel = hc[0], n_par = hc[1];
+    if (n_sel > n_src || n_par > n_sel || (n_sel && !n_par))
+        return fail(d, TSDF_EHIP, "coarsen: inconsistent counts (%llu parents of %llu bricks)",
+                    (unsigned long long)n_par, (unsigned long long)n_sel);
+    st.src_bricks = n_sel;
+    st.parent_bricks = n_par;
+    if (out) *out = st;
+    if (!n_sel) return TSDF_OK;
+    HIPCHK(d, launch_coarsen_flag(d->T, d->Pl, s->T, s->Pl, sel, min_children, min_weight, list,
+                                  n_par, ctr, flag, d->stream));
+    HIPCHK(d, hipMemcpyAsync(hc.data(), ctr, COARSEN_CTR_WORDS * 8, hipMemcpyDeviceToHost,
+                             d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    for (uint32_t q = 0; q < COARSEN_SHARDS; q++)  // the flag kernel's counter shards
+        for (int k = 0; k < 5; k++) h[k] += hc[COARSEN_CTR_HEAD + q * COARSEN_SHARD_WORDS + k];
+    if (h[0] > n_par || h[1] > h[0] || h[3] > h[2] || h[4] < h[2] || h[4] > 8 * h[2])
+        return fail(d, TSDF_EHIP, "coarsen: inconsistent counts (%llu touched of %llu parents)",
+                    h[0], (unsigned long long)n_par);
+    st.touched_bricks = h[0];
+    st.new_bricks = h[1];
+    st.coarse_voxels = h[2];
+    st.overlap_voxels = h[3];
+    st.child_voxels = h[4];
+    if (out) *out = st;
+    if (!apply || !st.touched_bricks) return TSDF_OK;
+
+    // room for the new bricks before anything is written (as the merge does)
+    const uint64_t need = n_dst + st.new_bricks;
+    if (need > d->T.max_bricks) {
+        if (!d->can_grow || (d->p.max_bricks_hard && need > d->p.max_bricks_hard) ||
+            need > 0xFFFFFFEFull)
+            return fail(d, TSDF_ENOMEM, "coarsen: %llu new bricks do not fit the pool (%llu of "
+                                        "%llu bricks in use) and it cannot grow",
+                        (unsigned long long)st.new_bricks, (unsigned long long)n_dst,
+                        (unsigned long long)d->T.max_bricks);
+        rc = grow_capacity(d, need);
+        if (rc) return rc;
+    }
+    HIPCHK(d, launch_merge_insert(d->T, list, n_par, flag, tslot, d->G, d->stream));
+    HIPCHK(d, launch_coarsen_apply(d->T, d->Pl, s->T, s->Pl, sel, min_children, min_weight,
+                                   merge_cap(d), list, n_par, tslot, d->stream));
+    HIPCHK(d, hipStreamSynchronize(d->stream));
+    return tsdf_sync(d);
+}
+
+extern "C" {
+
+int tsdf_coarsen_count(tsdf_ctx* dst, tsdf_ctx* src, const int32_t lo[3], const int32_t hi[3],
+                       int32_t side, uint32_t min_children, float min_weight,
+                       tsdf_coarsen_stats* out) {
+    return coarsen_impl(dst, src, lo, hi, side, min_children, min_weight, out, false);
+}
+
+int tsdf_coarsen_into(tsdf_ctx* dst, tsdf_ctx* src, const int32_t lo[3], const int32_t hi[3],
+                      int32_t side, uint32_t min_children, float min_weight,
+                      tsdf_coarsen_stats* out) {
+    return coarsen_impl(dst, src, lo, hi, side, min_children, min_weight, out, true);
 }
 
 }  // extern "C"

@@ -572,5 +572,33 @@ hipError_t launch_merge_apply(const Table& Td, const Pool& Pd, const Table& Ts, 
                               float max_w, const uint64_t* d_list, uint64_t n,
                               const uint32_t* d_flag, uint32_t* d_tslot, Globals* G,
                               hipStream_t st);
+// k_merge_insert alone (launch_merge_apply's first step; the coarsening shares it): the flagged
+// keys of d_list[0, n) into Td's table and pool, d_tslot[b] = the pool slot or INVALID_SLOT
+hipError_t launch_merge_insert(const Table& Td, const uint64_t* d_list, uint64_t n,
+                               const uint32_t* d_flag, uint32_t* d_tslot, Globals* G,
+                               hipStream_t st);
+// coarsening a map 2:1 into a map of twice the voxel size (tsdf_coarsen.hip;
+// include/tsdf_hip_coarsen.h; the index arithmetic and the scratch sizes: coarsen_plan.h).
+// d_ctr: COARSEN_CTR_WORDS u64, zeroed by the caller -- [0] selected source bricks, [1] distinct
+// parents (the list's entries), then from COARSEN_CTR_HEAD on COARSEN_SHARDS shards of
+// COARSEN_SHARD_WORDS words, of which the first five are touched bricks, new bricks, coarse
+// voxels, overlap voxels, child voxels (the caller adds the shards).
+struct CoarsenSel;
+constexpr uint32_t COARSEN_SHARDS = 64, COARSEN_SHARD_WORDS = 16, COARSEN_CTR_HEAD = 16;
+constexpr uint32_t COARSEN_CTR_WORDS = COARSEN_CTR_HEAD + COARSEN_SHARDS * COARSEN_SHARD_WORDS;
+// d_set: set_slots (a power of two, >= 2 * n_src) keys, EMPTY_KEY; d_list: n_src keys
+hipError_t launch_coarsen_parents(const uint64_t* d_src_keys, uint32_t n_src, const CoarsenSel& sel,
+                                  uint64_t* d_set, uint64_t set_slots, uint64_t* d_list,
+                                  unsigned long long* d_ctr, hipStream_t st);
+// d_flag[b] per parent: 0 no valid coarse voxel, 1 valid and held by dst, 3 valid and new
+hipError_t launch_coarsen_flag(const Table& Td, const Pool& Pd, const Table& Ts, const Pool& Ps,
+                               const CoarsenSel& sel, uint32_t min_children, float min_w,
+                               const uint64_t* d_list, uint64_t n, unsigned long long* d_ctr,
+                               uint32_t* d_flag, hipStream_t st);
+// the flagged parents of d_list[0, n), already inserted (d_tslot: their pool slots), fused
+hipError_t launch_coarsen_apply(const Table& Td, const Pool& Pd, const Table& Ts, const Pool& Ps,
+                                const CoarsenSel& sel, uint32_t min_children, float min_w,
+                                float max_w, const uint64_t* d_list, uint64_t n,
+                                const uint32_t* d_tslot, hipStream_t st);
 
 }  // namespace tsdf

@@ -250,6 +250,15 @@ hipError_t launch_merge_flag(const Table& Td, const Pool& Pd, const Table& Ts, c
     return hipGetLastError();
 }
 
+hipError_t launch_merge_insert(const Table& Td, const uint64_t* d_list, uint64_t n,
+                               const uint32_t* d_flag, uint32_t* d_tslot, Globals* G,
+                               hipStream_t st) {
+    if (!n) return hipSuccess;
+    k_merge_insert<<<capped_grid(n, MG_CAND_THREADS, 4096), MG_CAND_THREADS, 0, st>>>(
+        Td, d_list, n, d_flag, d_tslot, G);
+    return hipGetLastError();
+}
+
 hipError_t launch_merge_apply(const Table& Td, const Pool& Pd, const Table& Ts, const Pool& Ps,
                               const RayConst& R, const MergeXform& X, int mode, float min_w,
                               float max_w, const uint64_t* d_list, uint64_t n,
@@ -257,8 +266,8 @@ hipError_t launch_merge_apply(const Table& Td, const Pool& Pd, const Table& Ts, 
                               hipStream_t st) {
     if (!n) return hipSuccess;
     const MergeArgs A = merge_args(R, X, min_w, max_w);
-    k_merge_insert<<<capped_grid(n, MG_CAND_THREADS, 4096), MG_CAND_THREADS, 0, st>>>(
-        Td, d_list, n, d_flag, d_tslot, G);
+    const hipError_t e = launch_merge_insert(Td, d_list, n, d_flag, d_tslot, G, st);
+    if (e != hipSuccess) return e;
     const uint32_t grid = capped_grid(n, 1, MERGE_GRID_CAP);
     if (mode == 0)
         k_merge_apply<0><<<grid, BRICK_VOX, 0, st>>>(Pd, Td.max_bricks, Ts, Ps, A, d_list, n, d_tslot);

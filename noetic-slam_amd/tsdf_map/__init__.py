@@ -13,6 +13,7 @@ from .volume import (HipTSDFVolume, MergedTsdfIntegrator, SimpleTsdfIntegrator, 
                      sector_ids, select_sector)
 from .esdf import EsdfGrid, box_around, esdf_around  # noqa: F401
 from .gridmap import ColumnMap, columns_around  # noqa: F401
+from .lod import lod_pyramid  # noqa: F401
 from .mesh import mesh_tiles, write_ply  # noqa: F401
 from .submaps import fuse_submaps  # noqa: F401
 from .window import MemoryArchive, NpzArchive, SlidingWindow, cube_box  # noqa: F401

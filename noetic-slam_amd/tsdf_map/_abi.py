@@ -251,6 +251,30 @@ MERGE_SIGNATURES = {
 }
 
 
+# include/tsdf_hip_coarsen.h (TSDF_COARSEN_API): a map coarsened 2:1 into a map of twice the voxel
+# size, likewise a feature of libtsdf_hip.so outside the contract, declared on the HIP library only.
+COARSEN_SIDES = {"inside": 0, "outside": 1}  # TSDF_COARSEN_INSIDE / _OUTSIDE
+
+
+class CoarsenStats(C.Structure):
+    """tsdf_coarsen_stats (include/tsdf_hip_coarsen.h)."""
+    _fields_ = [("src_bricks", C.c_uint64), ("parent_bricks", C.c_uint64),
+                ("touched_bricks", C.c_uint64), ("new_bricks", C.c_uint64),
+                ("coarse_voxels", C.c_uint64), ("overlap_voxels", C.c_uint64),
+                ("child_voxels", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+COARSEN_SIGNATURES = {
+    "tsdf_coarsen_count": (C.c_int, [P, P, I3, I3, C.c_int32, C.c_uint32, C.c_float,
+                                     C.POINTER(CoarsenStats)]),
+    "tsdf_coarsen_into": (C.c_int, [P, P, I3, I3, C.c_int32, C.c_uint32, C.c_float,
+                                    C.POINTER(CoarsenStats)]),
+}
+
+
 # include/tsdf_hip_mesh.h (TSDF_MESH_API): the indexed triangle mesh (shared vertices, normals, a
 # voxel box), likewise a feature of libtsdf_hip.so outside the contract, declared on the HIP
 # library only.  Tables: MC_TABLES.

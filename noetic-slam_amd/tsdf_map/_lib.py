@@ -44,6 +44,9 @@ def load_hip_library(path=None):
     _abi.declare(lib, table=_abi.COLUMNS_SIGNATURES)
     # ... and merging a map into another under a rigid transform (include/tsdf_hip_merge.h)
     _abi.declare(lib, table=_abi.MERGE_SIGNATURES)
+    # ... and coarsening a map 2:1 into a map of twice the voxel size (include/tsdf_hip_coarsen.h)
+    _abi.declare(lib, table=_abi.COARSEN_SIGNATURES,
+                 optional=tuple(_abi.COARSEN_SIGNATURES))
     # ... and the indexed triangle mesh (include/tsdf_hip_mesh.h)
     _abi.declare(lib, table=_abi.MESH_SIGNATURES)
     # ... and motion-compensated Ouster frames (include/tsdf_hip_deskew.h)

@@ -661,6 +661,48 @@ class TSDFVolume:
             raise
         return st.as_dict()
 
+    # -- coarsening another map 2:1 into this one (include/tsdf_hip_coarsen.h) -------------------
+    def _coarsen_fn(self, name):
+        """An entry point of include/tsdf_hip_coarsen.h, detected by the symbol like `_sample_fn`."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (coarsening a map is part of "
+                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    def coarsen_from(self, src, min_children=1, min_weight=0.0, box=None, side="inside",
+                     dry_run=False):
+        """Fuse the 2:1 reduction of `src` (half this volume's voxel size) into this map, on the
+        GPU: a coarse voxel is the weight-weighted mean of its valid children (W > 0 and
+        W >= min_weight) when at least `min_children` of the eight are valid, with their mean
+        weight.  box = (lo, hi): only the source bricks lo <= b < hi (side "inside") or all the
+        others ("outside"), the predicate of `count_outside`.  dry_run: change nothing.
+        Returns the counts of tsdf_coarsen_stats as a dict; on TsdfError (TSDF_ENOMEM: the new
+        bricks do not fit and the pool cannot grow) both maps are as they were and the error's
+        `stats` holds the counts.  include/tsdf_hip_coarsen.h states the rules."""
+        if side not in _abi.COARSEN_SIDES:
+            raise ValueError("side must be one of %s" % sorted(_abi.COARSEN_SIDES))
+        fn = self._coarsen_fn("tsdf_coarsen_count" if dry_run else "tsdf_coarsen_into")
+        if not isinstance(src, TSDFVolume):
+            raise TypeError("src must be a TSDFVolume")
+        if src._lib is not self._lib:
+            raise ValueError("src belongs to another library")
+        if not 1 <= int(min_children) <= 8:
+            raise ValueError("min_children must be 1..8")
+        plo = phi = None
+        if box is not None:
+            lo, hi = self._box(*box)
+            plo, phi = lo.ctypes.data_as(_abi.I3), hi.ctypes.data_as(_abi.I3)
+        st = _abi.CoarsenStats()
+        rc = fn(self._ctx, src._ctx, plo, phi, _abi.COARSEN_SIDES[side], int(min_children),
+                float(min_weight), C.byref(st))
+        try:
+            self._check(rc, "coarsen_from")
+        except TsdfError as e:
+            e.stats = st.as_dict()
+            raise
+        return st.as_dict()
+
     def save(self, path):
         """Checkpoint: the brick map as .npz (keys, sdf, weight, parameters)."""
         c, s, w = self.export_bricks()
@@ -866,6 +908,30 @@ class HipTSDFVolume(TSDFVolume):
         out = self.empty_like()
         try:
             out.merge_from(self, pose, **kw)
+        except Exception:
+            out.close()
+            raise
+        return out
+
+    def coarsened(self, min_children=1, min_weight=0.0, **kw):
+        """A new volume with this one's parameters except `voxel_size` doubled, holding this map
+        coarsened 2:1: `coarsen_from(self, min_children, min_weight, **kw)` into an empty volume
+        (the truncation distance stays, as include/tsdf_hip_coarsen.h requires).  This volume is
+        not changed."""
+        self._coarsen_fn("tsdf_coarsen_into")
+        out = type(self).__new__(type(self))
+        out._lib = self._lib
+        out._ctx = C.c_void_p()
+        p = _abi.TsdfParams.from_buffer_copy(self.params)
+        p.voxel_size = 2.0 * float(self.params.voxel_size)
+        rc = self._lib.tsdf_create(C.byref(p), C.byref(out._ctx))
+        if rc != _abi.TSDF_OK:
+            out._ctx = C.c_void_p()
+            raise TsdfError(rc, "tsdf_create failed (coarsened)")
+        out._adopt(p)
+        out.tensor_device = self.tensor_device
+        try:
+            out.coarsen_from(self, min_children, min_weight, **kw)
         except Exception:
             out.close()
             raise

@@ -7,6 +7,16 @@ and leaves again is in the archive twice, one copy per generation (one `append` 
 and holds each brick at most once); `full_map()` merges the generations and the live bricks
 through `import_bricks`, whose weighted mean of two copies is the sum the unevicted map would
 hold (exact in the weights; the distances agree to the rounding of the mean).
+
+With `coarse` (a volume of twice the voxel size, include/tsdf_hip_coarsen.h) every eviction first
+fuses the 2:1 reduction of the leaving bricks into it, on the GPU: the space outside the window
+stays readable -- raycast, distance field, column maps -- at an eighth of the memory, without
+re-importing the archive.  Coarsening disjoint sets of bricks one after the other equals
+coarsening their union (rule 9 of the header), so the coarse map is exactly the coarsening of
+everything that has left the window, as long as no brick leaves twice.  A brick that is seen
+again and leaves again is fused a second time by the weighted mean, each generation's coarse value
+standing for that generation's voxels: an approximation of coarsening the summed fine bricks
+(DESIGN.md §24).
 """
 import ctypes as C
 import math
@@ -102,14 +112,21 @@ class NpzArchive:
 class SlidingWindow:
     """`volume` bounded to the cube of half-side radius_m around the latest scan origin: every
     `every` scans the bricks outside go to `archive` (anything with append(coords, sdf, weight);
-    default a MemoryArchive)."""
+    default a MemoryArchive).  coarse: a volume of twice the voxel size that takes the 2:1
+    reduction of every brick that leaves, before it leaves (None: nothing of the kind)."""
 
-    def __init__(self, volume, radius_m, every=8, archive=None):
+    def __init__(self, volume, radius_m, every=8, archive=None, coarse=None):
         if not radius_m >= 0:
             raise ValueError("radius_m must be >= 0")
         if int(every) < 1:
             raise ValueError("every must be >= 1")
         volume._prune_fn("tsdf_evict_outside")  # a volume that cannot evict says so here
+        if coarse is not None:
+            coarse._coarsen_fn("tsdf_coarsen_into")
+            if np.float32(coarse.voxel_size) != np.float32(2.0) * np.float32(volume.voxel_size):
+                raise ValueError("coarse must have twice the volume's voxel size (%g against %g)"
+                                 % (coarse.voxel_size, volume.voxel_size))
+        self.coarse = coarse
         self.volume = volume
         self.radius_m = float(radius_m)
         self.every = int(every)
@@ -126,6 +143,8 @@ class SlidingWindow:
     def evict(self, center):
         """Evict outside the cube around `center` now; returns the bricks archived."""
         lo, hi = cube_box(center, self.radius_m, self.volume.voxel_size)
+        if self.coarse is not None:
+            self.coarse.coarsen_from(self.volume, box=(lo, hi), side="outside")
         coords, sdf, weight = self.volume.evict_outside(lo, hi)
         self.archive.append(coords, sdf, weight)
         self.n_evicted += len(coords)
