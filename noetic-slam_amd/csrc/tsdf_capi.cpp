@@ -32,6 +32,7 @@
 #include "../../include/tsdf_hip_coarsen.h"
 #include "../../include/tsdf_hip_columns.h"
 #include "../../include/tsdf_hip_esdf.h"
+#include "../../include/tsdf_hip_frontier.h"
 #include "../../include/tsdf_hip_merge.h"
 #include "../../include/tsdf_hip_mesh.h"
 #include "../../include/tsdf_hip_prune.h"
@@ -43,6 +44,7 @@
 #include "ctx_plan.h"
 #include "columns_plan.h"
 #include "esdf_plan.h"
+#include "frontier_plan.h"
 #include "host_pack.h"
 #include "merge_plan.h"
 #include "mesh_plan.h"
@@ -2567,6 +2569,121 @@ static int mesh_impl(tsdf_ctx* c, float min_weight, int32_t table, const uint32_
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return TSDF_OK;
 }
+
+// ---- frontier voxels (include/tsdf_hip_frontier.h) -----------------------------------------------
+
+// What a frontier call wants: counts only, host outputs or device outputs.
+enum FrontierOut { FRONTIER_COUNT, FRONTIER_HOST, FRONTIER_DEVICE };
+
+static int frontier_impl(tsdf_ctx* c, const int64_t* lo, const int64_t* hi, float free_band,
+                         float min_weight, int32_t conn, int32_t min_unknown, int32_t* coords,
+                         uint8_t* n_unknown, int8_t* dir, uint64_t cap, tsdf_frontier_counts* out,
+                         FrontierOut mode) {
+    if (!c) return TSDF_EINVAL;
+    if (!out) return fail(c, TSDF_EINVAL, "frontier: null counts");
+    MeshBox B;
+    bool empty = false;
+    const int a = frontier_check(lo, hi, free_band, min_weight, conn, min_unknown, &B, &empty);
+    if (a != FRONTIER_ARG_OK) return fail(c, TSDF_EINVAL, "frontier: %s", frontier_arg_text(a));
+    if (c->p.n_sectors > 1)
+        return fail(c, TSDF_EINVAL, "frontier: the context holds one sector shard of the map "
+                                    "(n_sectors > 1); the frontier of a sharded field is not "
+                                    "supported");
+    if (c->brd_open)
+        return fail(c, TSDF_EINVAL, "frontier: a border reduce is open on this context: commit or "
+                                    "abort it first (tsdf_border_commit_device)");
+    uint64_t n_pool = 0;
+    int rc = pool_bricks(c, &n_pool);  // flushes and drains
+    if (rc) return rc;
+    *out = tsdf_frontier_counts{0, 0, 0, 0};
+    if (!n_pool || empty) return TSDF_OK;
+    if (n_pool >= 0xFFFFFFFFull) return fail(c, TSDF_EINVAL, "frontier: too many bricks");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the map's bricks in (z, y, x) order (the output's order), then those that intersect the box
+    std::vector<uint64_t> all(n_pool), keys;
+    HIPCHK(c, hipMemcpy(all.data(), c->T.brick_keys, n_pool * 8, hipMemcpyDeviceToHost));
+    std::sort(all.begin(), all.end(), brick_key_less_zyx);
+    for (uint64_t k : all)
+        if (mesh_brick_in_box(k, B, 0)) keys.push_back(k);
+    const uint64_t nb = keys.size();
+    out->n_bricks = nb;
+    if (!nb) return TSDF_OK;
+    Scratch tmp;
+    uint64_t *dk = nullptr, *doff = nullptr;
+    uint32_t* dcnt = nullptr;  // frontier voxels, then free voxels
+    hipError_t e = tmp.get(c, &dk, nb);
+    if (e == hipSuccess) e = tmp.get(c, &dcnt, 2 * nb);
+    if (e == hipSuccess) e = tmp.get(c, &doff, nb);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, TSDF_ENOMEM, "frontier: scratch allocation for %llu bricks failed",
+                    (unsigned long long)nb);
+    }
+    std::vector<uint32_t> cnt(2 * nb);
+    std::vector<uint64_t> off(nb);
+    HIPCHK(c, hipMemcpyAsync(dk, keys.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_frontier_count(c->T, c->Pl, dk, (uint32_t)nb, B, free_band, min_weight, conn,
+                                    min_unknown, dcnt, dcnt + nb, c->stream));
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), dcnt, 2 * nb * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    frontier_prefix(cnt.data(), nb, off.data(), &out->n_voxels, &out->n_frontier_bricks);
+    out->n_free = frontier_sum(cnt.data() + nb, nb);
+    const uint64_t nv = out->n_voxels;
+    if (mode == FRONTIER_COUNT || !nv) return TSDF_OK;
+    if (nv > cap)
+        return fail(c, TSDF_EOVERFLOW, "frontier has %llu voxels", (unsigned long long)nv);
+    if (!coords) return fail(c, TSDF_EINVAL, "frontier: null buffer");
+    int32_t* dc = coords;
+    uint8_t* dn = n_unknown;
+    int8_t* dd = dir;
+    if (mode == FRONTIER_HOST) {  // staged on the device
+        e = tmp.get(c, &dc, 3 * nv);
+        if (e == hipSuccess && n_unknown) e = tmp.get(c, &dn, nv);
+        if (e == hipSuccess && dir) e = tmp.get(c, &dd, 3 * nv);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, TSDF_ENOMEM, "frontier: output allocation for %llu voxels failed",
+                        (unsigned long long)nv);
+        }
+    }
+    HIPCHK(c, hipMemcpyAsync(doff, off.data(), nb * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, launch_frontier_emit(c->T, c->Pl, dk, (uint32_t)nb, B, free_band, min_weight, conn,
+                                   min_unknown, dcnt, doff, dc, dn, dd, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (mode == FRONTIER_HOST) {
+        HIPCHK(c, hipMemcpy(coords, dc, nv * 12, hipMemcpyDeviceToHost));
+        if (n_unknown) HIPCHK(c, hipMemcpy(n_unknown, dn, nv, hipMemcpyDeviceToHost));
+        if (dir) HIPCHK(c, hipMemcpy(dir, dd, nv * 3, hipMemcpyDeviceToHost));
+    }
+    return TSDF_OK;
+}
+
+extern "C" {
+
+int tsdf_frontier_count(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], float free_band,
+                        float min_weight, int32_t connectivity, int32_t min_unknown,
+                        tsdf_frontier_counts* out) {
+    return frontier_impl(c, lo, hi, free_band, min_weight, connectivity, min_unknown, nullptr,
+                         nullptr, nullptr, 0, out, FRONTIER_COUNT);
+}
+
+int tsdf_frontier_voxels(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3], float free_band,
+                         float min_weight, int32_t connectivity, int32_t min_unknown,
+                         int32_t* coords, uint8_t* n_unknown, int8_t* dir, uint64_t cap,
+                         tsdf_frontier_counts* out) {
+    return frontier_impl(c, lo, hi, free_band, min_weight, connectivity, min_unknown, coords,
+                         n_unknown, dir, cap, out, FRONTIER_HOST);
+}
+
+int tsdf_frontier_voxels_device(tsdf_ctx* c, const int64_t lo[3], const int64_t hi[3],
+                                float free_band, float min_weight, int32_t connectivity,
+                                int32_t min_unknown, int32_t* coords, uint8_t* n_unknown,
+                                int8_t* dir, uint64_t cap, tsdf_frontier_counts* out) {
+    return frontier_impl(c, lo, hi, free_band, min_weight, connectivity, min_unknown, coords,
+                         n_unknown, dir, cap, out, FRONTIER_DEVICE);
+}
+
+}  // extern "C"
 
 // ---- indexed mesh (include/tsdf_hip_mesh.h) ------------------------------------------------------
 

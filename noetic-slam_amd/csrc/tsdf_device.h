@@ -522,6 +522,19 @@ hipError_t launch_column_map(const Table& T, const Pool& Pl, const int64_t lo[3]
                              float band, float min_w, uint32_t min_occ, uint32_t min_free, float bg,
                              float vs, float* d_elev, float* d_ceil, uint16_t* d_n_occ,
                              uint16_t* d_n_free, uint8_t* d_flags, hipStream_t st);
+// frontier voxels of a box (tsdf_frontier.hip; include/tsdf_hip_frontier.h; the rules, the offset
+// table and the grid: frontier_plan.h).  d_keys: the nb listed bricks, sorted; d_cnt / d_fcnt: the
+// frontier and the free voxels of the box per listed brick; d_off: the exclusive prefix of d_cnt;
+// d_coords 3 int32, d_n_unknown 1 byte and d_dir 3 int8 per frontier voxel (the last two may be null)
+hipError_t launch_frontier_count(const Table& T, const Pool& Pl, const uint64_t* d_keys, uint32_t nb,
+                                 const MeshBox& B, float free_band, float min_weight, int conn,
+                                 int min_unknown, uint32_t* d_cnt, uint32_t* d_fcnt,
+                                 hipStream_t st);
+hipError_t launch_frontier_emit(const Table& T, const Pool& Pl, const uint64_t* d_keys, uint32_t nb,
+                                const MeshBox& B, float free_band, float min_weight, int conn,
+                                int min_unknown, const uint32_t* d_cnt, const uint64_t* d_off,
+                                int32_t* d_coords, uint8_t* d_n_unknown, int8_t* d_dir,
+                                hipStream_t st);
 hipError_t launch_fill_u32(uint32_t* p, uint32_t v, uint64_t n, hipStream_t st);
 hipError_t launch_fill_u64(uint64_t* p, uint64_t v, uint64_t n, hipStream_t st);
 // removing bricks (tsdf_prune.hip; include/tsdf_hip_prune.h), over the pool slots [0, n)

@@ -12,6 +12,7 @@ from .volume import (HipTSDFVolume, MergedTsdfIntegrator, SimpleTsdfIntegrator, 
                      extract_mesh_local, integrate_sectors, integrate_sectors_cloud,
                      sector_ids, select_sector)
 from .esdf import EsdfGrid, box_around, esdf_around  # noqa: F401
+from .frontier import FrontierSet, frontiers_around  # noqa: F401
 from .gridmap import ColumnMap, columns_around  # noqa: F401
 from .lod import lod_pyramid  # noqa: F401
 from .mesh import mesh_tiles, write_ply  # noqa: F401

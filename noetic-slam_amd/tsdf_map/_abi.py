@@ -296,6 +296,31 @@ MESH_SIGNATURES = {
 }
 
 
+# include/tsdf_hip_frontier.h (TSDF_FRONTIER_API): the frontier voxels of a map box (free voxels that
+# border the unknown), likewise a feature of libtsdf_hip.so outside the contract, declared on the
+# HIP library only.
+class FrontierCounts(C.Structure):
+    """tsdf_frontier_counts (include/tsdf_hip_frontier.h)."""
+    _fields_ = [("n_bricks", C.c_uint64), ("n_frontier_bricks", C.c_uint64),
+                ("n_voxels", C.c_uint64), ("n_free", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+I8P = C.POINTER(C.c_int8)
+FRONTIER_CONNECTIVITIES = (6, 18, 26)
+FRONTIER_SIGNATURES = {
+    "tsdf_frontier_count": (C.c_int, [P, L3, L3, C.c_float, C.c_float, C.c_int32, C.c_int32,
+                                      C.POINTER(FrontierCounts)]),
+    "tsdf_frontier_voxels": (C.c_int, [P, L3, L3, C.c_float, C.c_float, C.c_int32, C.c_int32, I3,
+                                       U8P, I8P, C.c_uint64, C.POINTER(FrontierCounts)]),
+    "tsdf_frontier_voxels_device": (C.c_int, [P, L3, L3, C.c_float, C.c_float, C.c_int32,
+                                              C.c_int32, P, P, P, C.c_uint64,
+                                              C.POINTER(FrontierCounts)]),
+}
+
+
 # include/tsdf_hip_deskew.h (TSDF_DESKEW_API): motion-compensated Ouster frames (the column headers
 # on the host, packets + one pose per column -> world points on the GPU), likewise a feature of
 # libtsdf_hip.so outside the contract, declared on the HIP library only.

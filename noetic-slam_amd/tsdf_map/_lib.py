@@ -49,6 +49,9 @@ def load_hip_library(path=None):
                  optional=tuple(_abi.COARSEN_SIGNATURES))
     # ... and the indexed triangle mesh (include/tsdf_hip_mesh.h)
     _abi.declare(lib, table=_abi.MESH_SIGNATURES)
+    # ... and the frontier voxels of a box (include/tsdf_hip_frontier.h)
+    _abi.declare(lib, table=_abi.FRONTIER_SIGNATURES,
+                 optional=tuple(_abi.FRONTIER_SIGNATURES))
     # ... and motion-compensated Ouster frames (include/tsdf_hip_deskew.h)
     _abi.declare(lib, table=_abi.DESKEW_SIGNATURES)
     if lib.tsdf_abi_version() != ABI_VERSION:

@@ -421,6 +421,61 @@ class TSDFVolume:
                        flags.ctypes.data_as(_abi.U8P)), "column_map")
         return ColumnMap(elev, ceil, n_occ, n_free, flags, lo, hi, self.voxel_size)
 
+    # -- frontier voxels (include/tsdf_hip_frontier.h) --------------------------------------------
+    def _frontier_fn(self, name):
+        """An entry point of include/tsdf_hip_frontier.h, detected by the symbol like `_sample_fn`."""
+        fn = getattr(self._lib, name, None)
+        if fn is None or fn.argtypes is None:
+            raise NotImplementedError("%s does not export %s (the frontier voxels are part of "
+                                      "libtsdf_hip.so only)" % (self._lib._name, name))
+        return fn
+
+    def _frontier_args(self, free_band, min_weight, connectivity, min_unknown):
+        if int(connectivity) not in _abi.FRONTIER_CONNECTIVITIES:
+            raise ValueError("connectivity must be 6, 18 or 26")
+        if not 1 <= int(min_unknown) <= int(connectivity):
+            raise ValueError("min_unknown must be in 1..connectivity")
+        band = self.voxel_size if free_band is None else free_band
+        return float(band), float(min_weight), int(connectivity), int(min_unknown)
+
+    def frontier_counts(self, lo=None, hi=None, free_band=None, min_weight=0.0, connectivity=6,
+                        min_unknown=1):
+        """tsdf_frontier_count: {"n_bricks", "n_frontier_bricks", "n_voxels", "n_free"} of the set
+        that `frontiers` would return; n_free is the explored free volume of the box in voxels."""
+        fn = self._frontier_fn("tsdf_frontier_count")
+        args = self._frontier_args(free_band, min_weight, connectivity, min_unknown)
+        lo, hi, plo, phi = self._mesh_box(lo, hi)
+        st = _abi.FrontierCounts()
+        self._check(fn(self._ctx, plo, phi, *args, C.byref(st)), "frontier_counts")
+        return st.as_dict()
+
+    def frontiers(self, lo=None, hi=None, free_band=None, min_weight=0.0, connectivity=6,
+                  min_unknown=1):
+        """The frontier voxels of the voxel box [lo, hi) (the whole map without one) as a
+        `frontier.FrontierSet`: the observed voxels (W > 0, W >= min_weight) with
+        sdf >= free_band (default: one voxel size) that have at least `min_unknown` unobserved
+        voxels among their 6, 18 or 26 neighbours.  Ordered by brick (z, y, x), then by in-brick
+        voxel.  Meaningful on maps integrated with space carving; without it the set is the rim
+        of the observed band.  include/tsdf_hip_frontier.h states the rules."""
+        from .frontier import FrontierSet
+        fn = self._frontier_fn("tsdf_frontier_voxels")
+        args = self._frontier_args(free_band, min_weight, connectivity, min_unknown)
+        lo, hi, plo, phi = self._mesh_box(lo, hi)
+        st = _abi.FrontierCounts()
+        for _ in range(2):
+            n = self.frontier_counts(lo, hi, *args)["n_voxels"]
+            coords = np.empty((n, 3), np.int32)
+            nu = np.empty(n, np.uint8)
+            d = np.empty((n, 3), np.int8)
+            rc = fn(self._ctx, plo, phi, *args, coords.ctypes.data_as(_abi.I3),
+                    nu.ctypes.data_as(_abi.U8P), d.ctypes.data_as(_abi.I8P), n, C.byref(st))
+            if rc == _abi.TSDF_EOVERFLOW:
+                continue
+            self._check(rc, "frontiers")
+            k = st.n_voxels
+            return FrontierSet(coords[:k], nu[:k], d[:k], st.as_dict(), self.voxel_size)
+        raise TsdfError(_abi.TSDF_EOVERFLOW, "frontiers: the map kept changing")
+
     def extract_triangle_mesh(self, fill_holes=True, min_weight=0.0, table="generated",
                               halo=None):
         """VDBVolume.extract_triangle_mesh: (vertices (3T, 3) float32, triangles (T, 3) int64) —
@@ -1018,6 +1073,30 @@ class HipTSDFVolume(TSDFVolume):
                        float(occ_band), float(min_weight), min_occ, min_free,
                        *[C.c_void_p(t.data_ptr()) for t in out]), "column_map_device")
         return tuple(out)
+
+    def frontiers_device(self, lo=None, hi=None, free_band=None, min_weight=0.0, connectivity=6,
+                         min_unknown=1):
+        """`frontiers` into device tensors on the volume's GPU: (coords (N, 3) int32, n_unknown
+        (N,) uint8, dir (N, 3) int8, counts dict), complete when the call returns."""
+        import torch
+        fn = self._frontier_fn("tsdf_frontier_voxels_device")
+        args = self._frontier_args(free_band, min_weight, connectivity, min_unknown)
+        lo, hi, plo, phi = self._mesh_box(lo, hi)
+        st = _abi.FrontierCounts()
+        for _ in range(2):
+            n = self.frontier_counts(lo, hi, *args)["n_voxels"]
+            coords = torch.empty((n, 3), dtype=torch.int32, device=self.tensor_device)
+            nu = torch.empty((n,), dtype=torch.uint8, device=self.tensor_device)
+            d = torch.empty((n, 3), dtype=torch.int8, device=self.tensor_device)
+            torch.cuda.synchronize(coords.device)
+            rc = fn(self._ctx, plo, phi, *args, C.c_void_p(coords.data_ptr()),
+                    C.c_void_p(nu.data_ptr()), C.c_void_p(d.data_ptr()), n, C.byref(st))
+            if rc == _abi.TSDF_EOVERFLOW:
+                continue
+            self._check(rc, "frontiers_device")
+            k = st.n_voxels
+            return coords[:k], nu[:k], d[:k], st.as_dict()
+        raise TsdfError(_abi.TSDF_EOVERFLOW, "frontiers_device: the map kept changing")
 
     def indexed_mesh_device(self, min_weight=0.0, table="generated", lo=None, hi=None,
                             normals=True):
